@@ -16,7 +16,15 @@ the flat gradient per step; each rank seeds its training noise differently;
 per-GPU batch is fixed (weak scaling) and `value` is the whole-job rate over
 the max-over-ranks time.
 
-Also reported (rank 0):
+A plain run sets up, warms up, times `--steps` steps and prints one JSON result
+line (`ms_per_step` is the time of one timed step).  `--dump-outputs DIR`
+writes what the last timed step computed (loss terms, reconstruction,
+likelihoods, aux loss, gradient norm and the updated parameters) as
+DIR/<name>.npy; the inputs, initial weights and training noise are seeded, so
+two builds run with the same arguments can be compared array for array.
+
+With `--full` also reported (rank 0), each from runs of its own after the
+timed steps:
   roofline      -- the step's dominant launch (the instrumented call with the
                    largest GPU time in a profiled step, compressai/_ledger.py),
                    replayed alone and timed with HIP events on the stream it
@@ -68,12 +76,20 @@ def parse():
                     help="rehearsal on a 1-GPU box: every rank on cuda:0 (needs --dist-backend gloo)")
     ap.add_argument("--serial-allreduce", action="store_true",
                     help="N > 1: one all-reduce after the backward instead of the two overlapped buckets")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled step (roofline, dominant_class, step_roofline, "
+                         "--ops-json) and the CPU baseline; off by default: a plain run only times its steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "a fixed seeded sample of any larger array)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="with --full: bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-batch", type=int, default=None, help="CPU baseline batch (default: the GPU per-step batch)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the profiled step (no roofline fields)")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="with --full: skip the profiled step (no roofline fields)")
     ap.add_argument("--keep-grads", action="store_true",
                     help="A/B: optimizers without zero_grad_in_step (zero_grad() fills the gradient buffers)")
-    ap.add_argument("--ops-json", default=None, help="write the profiled step's per-launch table here")
+    ap.add_argument("--ops-json", default=None, help="with --full: write the profiled step's per-launch table here")
     ap.add_argument("--roofline-only", action="store_true",
                     help="profile one step, then replay only its dominant launch --steps times "
                          "(for rocprofv3 --pmc passes)")
@@ -83,7 +99,12 @@ def parse():
     ap.add_argument("--replay", default=None,
                     help="with --roofline-only: replay this launch instead of the dominant one "
                          "('kind:index' of the ops table, e.g. conv_wgrad:3)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.ops_json and not args.full:
+        ap.error("--ops-json is the profiled step's table: it needs --full")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -278,6 +299,30 @@ def ops_table(led):
     return {"launches": rows, "by_kernel": kernels}
 
 
+DUMP_BUDGET = 48 << 20      # bytes of .npy payload in all (the limit is 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32.  The arrays share DUMP_BUDGET smallest first, each
+    taking at most an equal part of what is left; one larger than its part is written as a fixed sample: its
+    flattened elements at sorted indices drawn by a generator seeded with 0, so two runs with the same shapes
+    sample the same elements."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET // 4
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        cap = left // (len(todo) - i)
+        left -= min(cap, t.numel())
+        a = t.detach().to(dtype=torch.float32, device="cpu").contiguous().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_baseline(model_name, quality, batch, size, seconds):
     import torch
 
@@ -382,6 +427,11 @@ def main():
             out = net(x, guide, hidden) if multimodal else net(x)
             crit = criterion(out, x)
         state["loss"] = crit["loss"].detach()
+        if args.dump_outputs:
+            # under graph capture these are the graph's own output buffers: a replay leaves that step's values
+            state["out"] = {"x_hat": out["x_hat"].detach(),
+                            **{f"likelihoods_{k}": v.detach() for k, v in out["likelihoods"].items()},
+                            **{k: v.detach() for k, v in crit.items()}}
         if two_phase:
             sync.backward_head(crit["loss"])    # phase 0 (the synthesis' outermost piece): bucket 0 is final
         else:
@@ -393,6 +443,8 @@ def main():
     def opt_part():
         opt.step(max_norm=1.0)
         aux = net.aux_loss()
+        if args.dump_outputs:
+            state["aux_loss"] = aux.detach()
         aux.backward(loss_seed(aux))
         aux_opt.step()
 
@@ -495,9 +547,13 @@ def main():
         raise RuntimeError(f"non-finite loss {loss}")
     ms_per_step = dt / args.steps * 1e3
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9   # the timed steps' (and their graphs') peak
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step: the last timed step's results and the parameters it left
+        dump_outputs(args.dump_outputs, dict(state["out"], aux_loss=state["aux_loss"], grad_sqnorm=opt.sqnorm,
+                                             params=opt.flat, aux_params=aux_opt.flat))
 
     roof = step_roof = dom_class = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         led = profile_step(local_step)
         roof = dominant_roofline(led, workload)
         step_roof = step_roofline(led, ms_per_step)
@@ -506,7 +562,7 @@ def main():
             with open(args.ops_json, "w") as f:
                 json.dump(ops_table(led), f, indent=1)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not multimodal:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0 and not multimodal:
         cpu = cpu_baseline(args.model, args.quality, args.cpu_batch or args.batch, args.size, args.cpu_seconds)
     if rank == 0:
         value = world * args.batch * args.steps / dt

@@ -72,6 +72,37 @@ def test_bench_refuses_rank_mismatch():
     assert "--gpus 2 but the job has 1 ranks" in (r.stdout + r.stderr)
 
 
+def test_ops_json_needs_full():
+    """The per-launch table comes from the profiled step, which only a --full run takes."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--ops-json", "ops.json"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2
+    assert "needs --full" in r.stderr
+
+
+def test_dump_outputs_float32_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 <name>.npy; an array above its share of the budget is the same
+    seeded sample of its elements in every run, and the whole dump stays inside the budget."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.DUMP_BUDGET <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 2 * 100)      # 200 elements: 2 for `small`, 198 left for `big`
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    small = torch.tensor([[1.5, 2.5]], dtype=torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (198,)
+    assert np.array_equal(a, b) and np.all(np.diff(a) >= 0) and len(np.unique(a)) > 50
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (1, 2) and s.tolist() == [[1.5, 2.5]]
+    assert a.nbytes + s.nbytes <= 4 * 2 * 100
+
+
 def test_dominant_class_sums_launches_of_one_kernel():
     """bench.py's dominant_class: the kernel class with the largest SUMMED time wins over the single longest
     launch (cheng2020: hundreds of short convs vs one Adam launch), with its class-level roofline fraction."""
