@@ -197,6 +197,9 @@ SIGNATURES = {
     "cai_rd_loss_workspace_bytes": (_S, []),
     "cai_rd_loss_fwd": (_I, [POINTER(RdInputs), _F, _F, _P, _P, _S, _P]),
     "cai_rd_loss_bwd": (_I, [POINTER(RdInputs), _F, _F, _P, _P, _P, _P, POINTER(RdGrads), _P]),
+    "cai_msssim_workspace_bytes": (_S, [c_int32, c_int32, c_int32, c_int32]),
+    "cai_msssim_fwd": (_I, [_P, _P, c_int32, c_int32, c_int32, _F, c_int32, _P, _P, _P, _S, _P]),
+    "cai_msssim_bwd": (_I, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _S, _P]),
     "cai_sum_log": (_I, [_P, _I64, c_int32, c_int32, _P, _P, _S, _P]),
     "cai_sum_sqdiff": (_I, [_P, _P, _I64, _P, _P, _S, _P]),
     "cai_reduce_workspace_bytes": (_S, [_I64]),

@@ -1923,6 +1923,54 @@ class RdLossFn(torch.autograd.Function):
         return (dxh.view(xshape), None, None, None, *outs)
 
 
+class MsSsimFn(torch.autograd.Function):
+    """Five-scale MS-SSIM of two [B, C, H, W] images (csrc/msssim.hip; the definition of
+    compressai.utils.metrics.ms_ssim with its default window): returns (mean over the B*C planes, per-plane
+    values [B, C]).  The gradient goes to the first image only; the upstream gradients stay on the device."""
+
+    @staticmethod
+    def forward(ctx, x_hat, target, data_range: float = 1.0):
+        _check_cuda(x_hat, target)
+        if x_hat.shape != target.shape or x_hat.dim() != 4:
+            raise ValueError(f"ms_ssim expects two [B, C, H, W] tensors of one shape, got {tuple(x_hat.shape)} / "
+                             f"{tuple(target.shape)}")
+        if ctx.needs_input_grad[1]:
+            raise ValueError("MsSsimFn differentiates its first argument only (SSIM is symmetric: swap the two)")
+        xh = x_hat.float().contiguous()
+        tg = target.float().contiguous()
+        B, C, H, W = xh.shape
+        P = B * C
+        grad = 1 if ctx.needs_input_grad[0] else 0
+        nb = lib.cai_msssim_workspace_bytes(P, H, W, grad)
+        if nb == 0:
+            raise ValueError(f"cai_msssim_workspace_bytes: {lib.cai_last_error().decode(errors='replace')}")
+        ws = torch.empty(nb, dtype=torch.uint8, device=xh.device)
+        out = torch.empty(P + 1, dtype=torch.float32, device=xh.device)
+        _ledger.run(lambda: lib.cai_msssim_fwd(_p(xh), _p(tg), P, H, W, float(data_range), grad, _p(out),
+                                               _p(out[P:]), _p(ws), nb, _stream()),
+                    "msssim_fwd", "msssim_fwd_kernel", 0, 8 * xh.numel() + (nb if grad else 0), torch.float32)
+        ctx.save_for_backward(xh, tg, ws, out)
+        ctx.cfg = (x_hat.shape, x_hat.dtype)
+        ctx.set_materialize_grads(False)   # an unused output reaches backward as None; the kernel reads null as 0
+        return out[P], out[:P].view(B, C)
+
+    @staticmethod
+    def backward(ctx, g_mean, g_plane):
+        xh, tg, ws, out = ctx.saved_tensors
+        shape, dtype = ctx.cfg
+        if g_mean is None and g_plane is None:
+            return None, None, None
+        B, C, H, W = xh.shape
+        P = B * C
+        gm = None if g_mean is None else g_mean.float().contiguous()
+        gp = None if g_plane is None else g_plane.float().contiguous()
+        dx = torch.empty_like(xh)
+        _ledger.run(lambda: lib.cai_msssim_bwd(_p(xh), _p(tg), P, H, W, _p(out), _p(gm), _p(gp), _p(dx), _p(ws),
+                                               ws.numel(), _stream()),
+                    "msssim_bwd", "msssim_bwd_kernel", 0, 12 * xh.numel() + ws.numel(), torch.float32)
+        return dx.view(shape).to(dtype), None, None
+
+
 def _like_logical(d: torch.Tensor, buf: torch.Tensor, shape) -> torch.Tensor:
     """d has buf's memory layout; return it as a tensor of the likelihood's logical shape."""
     if tuple(buf.shape) == tuple(shape):

@@ -4,24 +4,44 @@ bpp = sum_k sum(log lik_k) / (-ln2 * N*H*W); mse = mean((x_hat - x)^2);
 loss = lmbda[q] * mse + bpp.  The forward is two HIP launches
 (cai_rd_loss_fwd: every sum in one grid, then a fixed-order fold that forms
 the three scalars), the backward one (cai_rd_loss_bwd).
+
+metric="ms-ssim" (upstream CompressAI's second distortion): loss =
+lmbda * (1 - ms_ssim(x_hat, x, data_range=1)) + bpp, the MS-SSIM and its
+gradient from csrc/msssim.hip (_ops.MsSsimFn), the bpp from the same RD
+kernels.  The lmbda table is the reference's, tuned for MSE on [0, 1]
+images: pass `lmbda` explicitly for MS-SSIM.
 """
 import torch.nn as nn
 
 from . import _ops
-from ._ops import RdLossFn, RdLossFnUnfused
+from ._ops import MsSsimFn, RdLossFn, RdLossFnUnfused
 
 LMBDA = [256, 512, 1024, 2048, 4096, 8192, 10240]   # train.py:65
+METRICS = ("mse", "ms-ssim")
 
 
 class RateDistortionLoss(nn.Module):
-    def __init__(self, q):
+    def __init__(self, q, metric="mse", lmbda=None):
         super().__init__()
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
         self.lmbda = list(LMBDA)
         self.q = q
+        self.metric = metric
+        self.lmbda_override = None if lmbda is None else float(lmbda)
 
     def forward(self, output, target):
         N, _, H, W = target.size()
         liks = list(output["likelihoods"].values())
         fn = RdLossFnUnfused if _ops._RD_UNFUSED else RdLossFn
-        loss, mse, bpp = fn.apply(output["x_hat"], target, float(self.lmbda[self.q]), N * H * W, *liks)
-        return {"bpp_loss": bpp, "mse_loss": mse, "loss": loss}
+        lmbda = float(self.lmbda[self.q]) if self.lmbda_override is None else self.lmbda_override
+        if self.metric == "mse":
+            loss, mse, bpp = fn.apply(output["x_hat"], target, lmbda, N * H * W, *liks)
+            return {"bpp_loss": bpp, "mse_loss": mse, "loss": loss}
+        # the bpp term from the RD kernels with their squared-error segment cut down to one pixel
+        # (lmbda 0: it contributes nothing, forward or backward)
+        one = target.detach().reshape(-1)[:1]
+        _, _, bpp = fn.apply(one, one, 0.0, N * H * W, *liks)
+        ms, _ = MsSsimFn.apply(output["x_hat"], target, 1.0)
+        loss = lmbda * (1.0 - ms) + bpp
+        return {"bpp_loss": bpp, "ms_ssim_loss": ms, "loss": loss}

@@ -653,6 +653,26 @@ int cai_sqdiff_bwd(const float* a, const float* b, int64_t n, const float* scale
                    float* ga, void* stream);
 
 /* =======================================================================
+ * MS-SSIM (csrc/msssim.hip): training distortion and evaluation metric.
+ * ======================================================================= */
+/* Five-scale MS-SSIM of `planes` fp32 image planes [planes][H][W] (planes = B * C, dense): 11-tap Gaussian
+ * window with sigma 1.5 ("valid"), K = (0.01, 0.03), weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333),
+ * 2x2 average pooling with padding side % 2 between scales, ReLU on the per-plane scale means.
+ * per_plane[planes] receives each plane's value, *mean their mean.  Fixed-order reductions, no atomics:
+ * the results are bit-reproducible.  Both sides must exceed 160.  with_grad != 0 keeps what cai_msssim_bwd
+ * needs in the workspace (a larger one: ask cai_msssim_workspace_bytes with the same flag; 0 = bad shape). */
+size_t cai_msssim_workspace_bytes(int32_t planes, int32_t H, int32_t W, int32_t with_grad);
+int cai_msssim_fwd(const float* x, const float* y, int32_t planes, int32_t H, int32_t W, float data_range,
+                   int32_t with_grad, float* per_plane, float* mean, void* workspace, size_t ws_bytes,
+                   void* stream);
+/* dx[planes][H][W] = d (g_mean * mean + sum_p g_plane[p] * per_plane[p]) / d x, from the workspace and the
+ * per_plane values a cai_msssim_fwd(with_grad = 1) on the same x, y left.  The upstream gradients are device
+ * values (either nullable = 0).  A plane with a scale mean <= 0 (clamped by the ReLU) gets exactly 0. */
+int cai_msssim_bwd(const float* x, const float* y, int32_t planes, int32_t H, int32_t W, const float* per_plane,
+                   const float* g_mean, const float* g_plane, float* dx, void* workspace, size_t ws_bytes,
+                   void* stream);
+
+/* =======================================================================
  * Optimiser over flat fp32 buffers (torch.optim.Adam semantics).
  * ======================================================================= */
 /* state[0] = sum(g^2) (fp32); workspace >= cai_reduce_workspace_bytes(n) */
