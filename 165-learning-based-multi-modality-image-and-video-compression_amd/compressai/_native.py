@@ -67,6 +67,18 @@ JOB_NONE, JOB_WGRAD, JOB_GDN, JOB_EDGE = 0, 1, 2, 3           # cai_reduce_job k
 GC_SCALES_RELU = 16                                              # cai_gc_bwd mode flag
 
 
+class ArArgs(Structure):
+    """cai_ar_args: the fused autoregressive coder's operands (include/cai.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "W", "M", "Cp", "Cx", "C1", "C2")]
+                + [(n, c_void_p) for n in ("y", "params", "w_ctx", "b_ctx", "w1p", "w1c", "b1", "w2", "b2", "w3", "b3")]
+                + [("slope", c_float), ("scale_bound", c_float), ("scale_table", c_void_p), ("n_scales", c_int32),
+                   ("cdf_stride", c_int32)]
+                + [(n, c_void_p) for n in ("y_hat", "symbols", "indexes", "scales", "means", "data")]
+                + [("data_bytes", c_int64)]
+                + [(n, c_void_p) for n in ("offsets", "lengths", "cdfs", "cdf_sizes", "cdf_offsets")]
+                + [("n_cdfs", c_int32), ("status", c_void_p)])
+
+
 class ReduceJob(Structure):
     _fields_ = [("kind", c_int32), ("nblocks", c_int32), ("i", c_int32 * 10), ("f", c_float * 2), ("p", c_void_p * 6)]
 
@@ -200,6 +212,9 @@ SIGNATURES = {
     "cai_msssim_workspace_bytes": (_S, [c_int32, c_int32, c_int32, c_int32]),
     "cai_msssim_fwd": (_I, [_P, _P, c_int32, c_int32, c_int32, _F, c_int32, _P, _P, _P, _S, _P]),
     "cai_msssim_bwd": (_I, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _S, _P]),
+    "cai_ar_workspace_bytes": (_S, [POINTER(ArArgs)]),
+    "cai_ar_encode": (_I, [POINTER(ArArgs), _P, _S, _P]),
+    "cai_ar_decode": (_I, [POINTER(ArArgs), _P, _S, _P]),
     "cai_sum_log": (_I, [_P, _I64, c_int32, c_int32, _P, _P, _S, _P]),
     "cai_sum_sqdiff": (_I, [_P, _P, _I64, _P, _P, _S, _P]),
     "cai_reduce_workspace_bytes": (_S, [_I64]),

@@ -29,7 +29,7 @@ import torch
 from . import _ledger
 from ._native import (ACT_LEAKY, ACT_NONE, ACT_RELU, BF16, F32, MASK_BEFORE_RES, MASK_LEAKY, MASK_NONE, MASK_POS,
                       Q_DEQUANTIZE, Q_NOISE,
-                      GC_SCALES_RELU, JOB_EDGE, JOB_GDN, JOB_NONE, JOB_WGRAD, NOISE_BUF, NOISE_DRAW, NOISE_REPLAY, ConvGeom, EbGrads, EbParams, NoiseSrc, RdGrads,
+                      GC_SCALES_RELU, JOB_EDGE, JOB_GDN, JOB_NONE, JOB_WGRAD, NOISE_BUF, NOISE_DRAW, NOISE_REPLAY, ArArgs, ConvGeom, EbGrads, EbParams, NoiseSrc, RdGrads,
                       RdInputs, ReduceJob, ResunitArgs, ResunitWgradArgs, WgradCall, lib)
 
 _VP = ctypes.c_void_p
@@ -1969,6 +1969,165 @@ class MsSsimFn(torch.autograd.Function):
                                                ws.numel(), _stream()),
                     "msssim_bwd", "msssim_bwd_kernel", 0, 12 * xh.numel() + ws.numel(), torch.float32)
         return dx.view(shape).to(dtype), None, None
+
+
+# ---------------------------------------------------------------------------
+# fused autoregressive entropy coding of the context models -- csrc/ar_coder.hip
+# ---------------------------------------------------------------------------
+
+AR_MAX_SCALES = 256                       # the kernel's scale-table cap (csrc/ar_coder.hip)
+AR_TAPS = tuple((ky, kx) for ky in (0, 1) for kx in range(5)) + ((2, 0), (2, 1))   # mask "A" of a 5x5 kernel
+AR_STATUS = {1: "truncated or corrupt stream", 2: "cdf index out of range", 3: "invalid cdf size",
+             4: "stream length must be a multiple of 4 bytes, at least the 8-byte rANS state"}
+
+
+def _ar_rows(w2d: torch.Tensor) -> torch.Tensor:
+    """[O, K] -> the kernel's [K, pad4(O)] fp32 layout (input-major rows, zero columns past O)."""
+    O, K = w2d.shape
+    out = torch.zeros(K, (O + 3) // 4 * 4, dtype=torch.float32, device=w2d.device)
+    out[:, :O] = w2d.detach().float().t()
+    return out
+
+
+def _ar_bias(b: Optional[torch.Tensor], n: int, device) -> torch.Tensor:
+    return torch.zeros(n, device=device) if b is None else b.detach().float().contiguous()
+
+
+class ArPack:
+    """What cai_ar_encode / cai_ar_decode read besides the latents, packed once per compress() / decompress():
+    the masked context conv's 12 causal taps, the three 1x1 layers (the first split into its params and context
+    halves), the scale table and the CDF tables, all on the device."""
+
+    def __init__(self, ctx_weight, ctx_bias, layers, slope, scale_table, scale_bound, cdfs, cdf_sizes, cdf_offsets):
+        _check_cuda(ctx_weight, scale_table, cdfs)
+        dev = ctx_weight.device
+        (w1, b1), (w2, b2), (w3, b3) = layers
+        self.Cx, self.M = int(ctx_weight.shape[0]), int(ctx_weight.shape[1])
+        self.C1, self.C2, C0, C3 = int(w1.shape[0]), int(w2.shape[0]), int(w1.shape[1]), int(w3.shape[0])
+        self.Cp = C0 - self.Cx
+        if (tuple(ctx_weight.shape[2:]) != (5, 5) or self.Cp <= 0 or w2.shape[1] != self.C1 or w3.shape[1] != self.C2
+                or C3 != 2 * self.M):
+            raise ValueError(f"fused AR coding: unsupported widths (context conv {tuple(ctx_weight.shape)}, 1x1 stack "
+                             f"{C0}->{self.C1}->{self.C2}->{C3}, latent channels {self.M})")
+        taps = torch.stack([ctx_weight.detach().float()[:, :, ky, kx] for ky, kx in AR_TAPS], 0)   # [12, Cx, M]
+        self.w_ctx = _ar_rows(taps.permute(1, 0, 2).reshape(self.Cx, 12 * self.M))
+        w1 = w1.detach().float().reshape(self.C1, C0)
+        self.w1p, self.w1c = _ar_rows(w1[:, :self.Cp]), _ar_rows(w1[:, self.Cp:])
+        self.w2, self.w3 = _ar_rows(w2.reshape(self.C2, self.C1)), _ar_rows(w3.reshape(C3, self.C2))
+        self.b_ctx, self.b1 = _ar_bias(ctx_bias, self.Cx, dev), _ar_bias(b1, self.C1, dev)
+        self.b2, self.b3 = _ar_bias(b2, self.C2, dev), _ar_bias(b3, C3, dev)
+        self.slope, self.scale_bound = float(slope), float(scale_bound)
+        self.scale_table = scale_table.detach().float().contiguous()
+        self.cdfs = cdfs.int().contiguous()
+        self.cdf_sizes = cdf_sizes.reshape(-1).int().contiguous()
+        self.cdf_offsets = cdf_offsets.reshape(-1).int().contiguous()
+        if not 1 <= self.scale_table.numel() <= AR_MAX_SCALES:
+            raise ValueError(f"fused AR coding: scale table of {self.scale_table.numel()} entries "
+                             f"(1..{AR_MAX_SCALES} supported)")
+        if self.cdfs.dim() != 2 or not (self.cdfs.shape[0] == self.cdf_sizes.numel() == self.cdf_offsets.numel()
+                                        >= self.scale_table.numel()):
+            raise ValueError("fused AR coding: CDF tables do not match the scale table (run update() first)")
+
+    def args(self, params: torch.Tensor) -> "ArArgs":
+        B, H, W, Cp = params.shape
+        if Cp != self.Cp:
+            raise ValueError(f"fused AR coding: params have {Cp} channels, the entropy parameters expect {self.Cp}")
+        a = ArArgs()
+        a.B, a.H, a.W, a.M, a.Cp, a.Cx, a.C1, a.C2 = B, H, W, self.M, self.Cp, self.Cx, self.C1, self.C2
+        a.params = params.data_ptr()
+        for n in ("w_ctx", "b_ctx", "w1p", "w1c", "b1", "w2", "b2", "w3", "b3", "scale_table", "cdfs", "cdf_sizes",
+                  "cdf_offsets"):
+            setattr(a, n, getattr(self, n).data_ptr())
+        a.slope, a.scale_bound, a.n_scales = self.slope, self.scale_bound, self.scale_table.numel()
+        a.cdf_stride, a.n_cdfs = self.cdfs.shape[1], self.cdfs.shape[0]
+        return a
+
+    def weight_bytes(self) -> int:
+        return 4 * sum(t.numel() for t in (self.w_ctx, self.w1p, self.w1c, self.w2, self.w3))
+
+
+def _ar_pm(t: torch.Tensor) -> torch.Tensor:
+    """Logical [B, C, H, W] -> dense fp32 [B, H, W, C]."""
+    return t.float().permute(0, 2, 3, 1).contiguous()
+
+
+def _ar_launch(fn, name: str, pack: ArPack, a: "ArArgs", device):
+    nb = lib.cai_ar_workspace_bytes(ctypes.byref(a))
+    if nb == 0:
+        raise ValueError(f"cai_ar_workspace_bytes: {lib.cai_last_error().decode(errors='replace')}")
+    ws = torch.empty(nb, dtype=torch.uint8, device=device)
+    npix = a.B * a.H * a.W
+    # every pixel streams the scan's weights once; the hoisted half is one small GEMM
+    nbytes = float(a.H * a.W) * (pack.weight_bytes() - 4 * pack.w1p.numel()) + 4.0 * npix * (a.Cp + 4 * a.M + a.C1)
+    flops = 2.0 * npix * pack.weight_bytes() / 4
+    _ledger.run(lambda: fn(ctypes.byref(a), _p(ws), nb, _stream()), name, f"ar_scan_kernel<{name[3:]}>",
+                flops, nbytes, torch.float32, f"AR {a.M}ch {a.H}x{a.W} B={a.B}")
+
+
+def ar_encode(pack: ArPack, y: torch.Tensor, params: torch.Tensor, with_params: bool = False) -> dict:
+    """The autoregressive scan of a batch in one launch (csrc/ar_coder.hip): y [B, M, H, W], params
+    [B, Cp, H, W] -> {"symbols", "indexes"} int32 [B, H*W*M] in the coder's order (pixel-major, channel-minor),
+    "y_hat" [B, M, H, W]; with_params adds the per-element "scales" and "means" [B, H, W, M] the kernel used."""
+    _check_cuda(y, params)
+    ypm, ppm = _ar_pm(y), _ar_pm(params)
+    B, H, W, M = ypm.shape
+    if M != pack.M or tuple(ppm.shape[:3]) != (B, H, W):
+        raise ValueError(f"ar_encode: y {tuple(y.shape)} / params {tuple(params.shape)} do not match the model")
+    dev = ypm.device
+    out = {"symbols": torch.empty(B, H * W * M, dtype=torch.int32, device=dev),
+           "indexes": torch.empty(B, H * W * M, dtype=torch.int32, device=dev), "y_hat": torch.empty_like(ypm)}
+    if with_params:
+        out["scales"], out["means"] = torch.empty_like(ypm), torch.empty_like(ypm)
+    a = pack.args(ppm)
+    a.y = ypm.data_ptr()
+    for n, t in out.items():
+        setattr(a, n, t.data_ptr())
+    _ar_launch(lib.cai_ar_encode, "ar_encode", pack, a, dev)
+    out["y_hat"] = out["y_hat"].permute(0, 3, 1, 2)
+    return out
+
+
+def ar_decode(pack: ArPack, strings: Sequence[bytes], params: torch.Tensor, with_params: bool = False,
+              check: bool = True) -> dict:
+    """Inverse of ar_encode + the rANS coder: the streams of a batch are decoded inside the scan kernel.
+    -> {"y_hat" [B, M, H, W], "status" int32 [B] (host)}; with_params adds symbols, indexes, scales, means.
+    A non-zero status raises the host decoder's ValueError unless check is False."""
+    _check_cuda(params)
+    ppm = _ar_pm(params)
+    B, H, W, _ = ppm.shape
+    if len(strings) != B:
+        raise ValueError("ar_decode: one string per batch element expected")
+    dev, M = ppm.device, pack.M
+    lens = [len(s) for s in strings]
+    offs, total = [], 0
+    for n in lens:                      # every stream starts on a 4-byte boundary
+        offs.append(total)
+        total += (n + 3) // 4 * 4
+    blob = bytearray(max(total, 4))
+    for s, o in zip(strings, offs):
+        blob[o:o + len(s)] = bytes(s)
+    data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+    meta = torch.tensor([offs, lens], dtype=torch.int64).to(dev)
+    out = {"y_hat": torch.empty(B, H, W, M, dtype=torch.float32, device=dev)}
+    if with_params:
+        for n in ("symbols", "indexes"):
+            out[n] = torch.empty(B, H * W * M, dtype=torch.int32, device=dev)
+        for n in ("scales", "means"):
+            out[n] = torch.empty_like(out["y_hat"])
+    status = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    a = pack.args(ppm)
+    for n, t in out.items():
+        setattr(a, n, t.data_ptr())
+    a.data, a.data_bytes, a.offsets, a.lengths = data.data_ptr(), total, meta[0].data_ptr(), meta[1].data_ptr()
+    a.status = status.data_ptr()
+    _ar_launch(lib.cai_ar_decode, "ar_decode", pack, a, dev)
+    out["status"] = status.cpu()
+    if check:
+        for i, st in enumerate(out["status"].tolist()):
+            if st != 0:
+                raise ValueError(f"cai_ar_decode: item {i}: {AR_STATUS.get(st, f'status {st}')}")
+    out["y_hat"] = out["y_hat"].permute(0, 3, 1, 2)
+    return out
 
 
 def _like_logical(d: torch.Tensor, buf: torch.Tensor, shape) -> torch.Tensor:

@@ -468,6 +468,54 @@ class _ARCoding:
     entropy-parameter stack run on the HIP kernels, fp32, so encoder and decoder agree exactly."""
 
     _AR_SPEC = None
+    AR_BACKENDS = ("serial", "fused")
+    _ar_backend = "serial"
+
+    @property
+    def ar_backend(self) -> str:
+        """"serial" (default): the reference's per-pixel loop on the conv kernels, coded on the host.
+        "fused": the whole scan of the batch in one launch (csrc/ar_coder.hip), decoding on the device.
+        The two sum the entropy parameters in different orders, so a stream must be read by the backend that
+        wrote it."""
+        return self._ar_backend
+
+    @ar_backend.setter
+    def ar_backend(self, name: str):
+        if name not in self.AR_BACKENDS:
+            raise ValueError(f"ar_backend must be one of {self.AR_BACKENDS}, got {name!r}")
+        self._ar_backend = name
+
+    def _ar_fused_pack(self, params):
+        """Check that the model is what the fused kernel computes -- a 5x5 mask-"A" context conv and three 1x1
+        convs with one LeakyReLU slope between them, reading cat(params, ctx) -- and pack it for the kernel."""
+        from .. import _ops
+
+        cp, ep, gc = self.context_prediction, self.entropy_parameters, self.gaussian_conditional
+        mods = list(ep) if isinstance(ep, nn.Sequential) else []
+        ok = (isinstance(cp, MaskedConv2d) and tuple(cp.kernel_size) == (5, 5) and tuple(cp.stride) == (1, 1)
+              and tuple(cp.padding) == (2, 2) and tuple(cp.dilation) == (1, 1) and cp.groups == 1
+              and bool((cp.mask[0, 0] != 0).flatten()[:12].all()) and not bool(cp.mask[0, 0].flatten()[12:].any())
+              and len(mods) == 5 and all(isinstance(mods[i], nn.Conv2d) for i in (0, 2, 4))
+              and all(tuple(mods[i].kernel_size) == (1, 1) and tuple(mods[i].stride) == (1, 1)
+                      and tuple(mods[i].padding) == (0, 0) and mods[i].groups == 1 for i in (0, 2, 4))
+              and all(isinstance(mods[i], nn.LeakyReLU) for i in (1, 3))
+              and mods[1].negative_slope == mods[3].negative_slope
+              and mods[0].in_channels == params.size(1) + cp.out_channels
+              and mods[2].in_channels == mods[0].out_channels and mods[4].in_channels == mods[2].out_channels
+              and mods[4].out_channels == 2 * cp.in_channels)
+        if not ok:
+            raise ValueError('ar_backend="fused" needs a 5x5 mask-A context_prediction and an entropy_parameters stack '
+                             "of three 1x1 convs with LeakyReLU between them, from cat(params, ctx) to 2M channels; "
+                             f"got {cp} / {ep}")
+        if not params.is_cuda or not cp.weight.is_cuda:
+            raise ValueError('ar_backend="fused" runs on the GPU only (model and input on a CPU device); there is no '
+                             "CPU fallback, an encoder and a decoder on different backends would not agree")
+        gc._check_cdf_size()
+        gc._check_cdf_length()
+        gc._check_offsets_size()
+        return _ops.ArPack(cp.weight.data * cp.mask, cp.bias, [(mods[i].weight, mods[i].bias) for i in (0, 2, 4)],
+                           mods[1].negative_slope, gc.scale_table, gc._scale_bound_value, gc._quantized_cdf,
+                           gc._cdf_length, gc._offset)
 
     def _ar_params(self, y_crop, p):
         """Entropy parameters of the centre pixel of a 5x5 crop: masked context conv
@@ -484,12 +532,19 @@ class _ARCoding:
 
     @staticmethod
     def _warn_gpu(model):
+        if getattr(model, "ar_backend", "serial") == "fused":
+            if next(model.parameters()).device.type != "cuda":
+                raise ValueError('ar_backend="fused" runs on the GPU only and the model is on a CPU device; there '
+                                 "is no CPU fallback (an encoder and a decoder on different backends would not agree)")
+            return
         if next(model.parameters()).device != torch.device("cpu"):
             warnings.warn("Inference on GPU is not recommended for the autoregressive models (the entropy coder is "
                           "run sequentially on CPU).")
 
     def _ar_encode_all(self, y, params):
         """y_strings of a batch (google.py:542-561)."""
+        if self.ar_backend == "fused":
+            return self._ar_encode_fused(y, params)["strings"]
         cp = self.context_prediction
         cp.weight.data *= cp.mask          # MaskedConv2d semantics (layers.py:75-78)
         kernel_size = 5
@@ -501,6 +556,10 @@ class _ARCoding:
 
     def _ar_decode_all(self, y_strings, params):
         """y_hat of a batch (google.py:622-650)."""
+        if self.ar_backend == "fused":
+            from .. import _ops
+
+            return _ops.ar_decode(self._ar_fused_pack(params), y_strings, params)["y_hat"]
         cp = self.context_prediction
         cp.weight.data *= cp.mask
         kernel_size = 5
@@ -511,6 +570,17 @@ class _ARCoding:
         for i, y_string in enumerate(y_strings):
             self._decompress_ar(y_string, y_hat[i:i + 1], params[i:i + 1], y_height, y_width, kernel_size, padding)
         return F.pad(y_hat, (-padding, -padding, -padding, -padding))
+
+    def _ar_encode_fused(self, y, params, with_params=False):
+        """One kernel call for the batch, then the host coder on its symbols: {"strings", "y_hat", "symbols",
+        "indexes"} (+ "scales", "means" with with_params)."""
+        from .. import _coder, _ops
+
+        out = _ops.ar_encode(self._ar_fused_pack(params), y, params, with_params)
+        B = y.size(0)
+        out["strings"] = _coder.encode_streams(out["symbols"].cpu().numpy(), out["indexes"].cpu().numpy(),
+                                               self.gaussian_conditional._tables(), B)
+        return out
 
     def _compress_ar(self, y_hat, params, height, width, kernel_size, padding):
         """google.py:565-608."""

@@ -281,7 +281,7 @@ def _device(args) -> str:
     return "cuda"
 
 
-def _load_nets(model: str, paths: Sequence[str], channel: int, device):
+def _load_nets(model: str, paths: Sequence[str], channel: int, device, ar_backend: str = "serial"):
     from compressai.utils.eval_model.__main__ import load_checkpoint
 
     if model == "Master_compresser":
@@ -295,6 +295,8 @@ def _load_nets(model: str, paths: Sequence[str], channel: int, device):
         nets = [load_checkpoint(model, paths[0], channel=channel).to(device)]
     for n in nets:
         n.update()
+        if hasattr(n, "ar_backend"):
+            n.ar_backend = ar_backend
     return nets if model == "Master_compresser" else nets[0]
 
 
@@ -306,20 +308,34 @@ def _common_args(p: argparse.ArgumentParser):
     p.add_argument("-c", "--coder", default="ans")
     p.add_argument("--cuda", action="store_true", help="accepted for compatibility: this build always runs on the GPU")
     p.add_argument("-o", "--output", required=True)
+    p.add_argument("--ar-backend", choices=("serial", "fused"), default="serial",
+                   help="autoregressive coding of the context models: the per-pixel loop, or the whole scan in one "
+                        "kernel launch; a stream must be decoded with the backend that encoded it")
 
 
-def encode(argv):
-    import compressai
-
+def encode_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Encode an image to a bit-stream")
     p.add_argument("input")
     p.add_argument("-m", "--metric", choices=list(METRIC_IDS), default="mse")
     p.add_argument("-q", "--quality", type=int, default=3)
     _common_args(p)
-    a = p.parse_args(argv)
+    return p
+
+
+def decode_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Decode a bit-stream to an image")
+    p.add_argument("input")
+    _common_args(p)
+    return p
+
+
+def encode(argv):
+    import compressai
+
+    a = encode_parser().parse_args(argv)
     compressai.set_entropy_coder(a.coder)
     device = _device(a)
-    net = _load_nets(a.model, a.path, a.channel, device)
+    net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)
     x = load_master_image(a.input, a.channel, device)
     guided = None
     if a.model == "Master_compresser":
@@ -332,13 +348,10 @@ def encode(argv):
 def decode(argv):
     import compressai
 
-    p = argparse.ArgumentParser(description="Decode a bit-stream to an image")
-    p.add_argument("input")
-    _common_args(p)
-    a = p.parse_args(argv)
+    a = decode_parser().parse_args(argv)
     compressai.set_entropy_coder(a.coder)
     device = _device(a)
-    net = _load_nets(a.model, a.path, a.channel, device)
+    net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)
     guided = None
     if a.model == "Master_compresser":
         if a.guided is None:

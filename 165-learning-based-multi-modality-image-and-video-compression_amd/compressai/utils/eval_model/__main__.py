@@ -241,6 +241,9 @@ def setup_args():
     parent.add_argument("--guided-checkpoint", type=str, default=None, help="Guided_compresser checkpoint")
     parent.add_argument("--guided-channel", type=int, default=None)
     parent.add_argument("-o", "--output", type=str, default=None, help="append the JSON result to this file")
+    parent.add_argument("--ar-backend", choices=("serial", "fused"), default="serial",
+                        help="entropy coding of the autoregressive models: the per-pixel loop, or the whole scan "
+                             "in one kernel launch (both ends of a stream on the same backend)")
     parser = argparse.ArgumentParser(description="Evaluate a model on an image dataset.", add_help=True)
     sub = parser.add_subparsers(help="model source", dest="source")
     pre = sub.add_parser("pretrained", parents=[parent])
@@ -287,12 +290,17 @@ def main(argv):
             if not args.entropy_estimation:
                 model.update()
                 model_g.update()
+            for m in (model, model_g):
+                if hasattr(m, "ar_backend"):
+                    m.ar_backend = args.ar_backend
             metrics = eval_model_rgbt(model, model_g, list(zip(filepaths, gfiles)), args.entropy_estimation,
                                       args.half)
         else:
             model = load_checkpoint(args.architecture, run, args.channel).to(device)
             if not args.entropy_estimation:
                 model.update()
+            if hasattr(model, "ar_backend"):
+                model.ar_backend = args.ar_backend
             metrics = eval_model(model, filepaths, args.entropy_estimation, args.half)
         for k, v in metrics.items():
             results[k].append(v)

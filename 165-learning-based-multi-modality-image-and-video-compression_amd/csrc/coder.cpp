@@ -15,6 +15,7 @@
 // mode) already on the host.
 #include "cai.h"
 #include "cai_coder.h"
+#include "rans_decode.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -34,10 +35,11 @@ int fail(int code, std::string msg) {
     return code;
 }
 
-constexpr uint32_t kScaleBits = 16;                 // rans_interface.cpp:49
-constexpr uint32_t kBypassBits = 4;                 // rans_interface.cpp:51
-constexpr uint32_t kMaxBypass = (1u << kBypassBits) - 1;
-constexpr uint64_t kRansL = 1ull << 31;             // rans64.h:59
+using cai_rans::kBypassBits;
+using cai_rans::kMaxBypass;
+using cai_rans::kRansL;
+using cai_rans::kScaleBits;
+using cai_rans::DecState;
 
 // ---------------------------------------------------------------------------
 // quantized CDF (ops.cpp:40-109), same integer arithmetic step by step
@@ -234,104 +236,26 @@ int flush_syms(const std::vector<RansSym>& syms, uint8_t* out, int64_t cap, int6
     return CAI_OK;
 }
 
-struct DecState {
-    uint64_t x = 0;
-    const uint32_t* ptr = nullptr;
-    const uint32_t* end = nullptr;
-};
-
-inline bool refill(DecState& d) {
-    if (d.x < kRansL) {
-        if (d.ptr >= d.end) return false;
-        d.x = (d.x << 32) | *d.ptr++;
-    }
-    return true;
-}
-
 int dec_init(DecState& d, const uint32_t* words, int64_t nwords, std::string& err) {
-    if (nwords < 2) {
+    if (!cai_rans::dec_init(d, words, nwords)) {
         err = "stream shorter than the 8-byte rANS state";
         return CAI_EINVAL;
     }
-    d.x = (uint64_t)words[0] | ((uint64_t)words[1] << 32);
-    d.ptr = words + 2;
-    d.end = words + nwords;
     return CAI_OK;
 }
 
-// rans_interface.cpp:89-105
-inline bool get_bits(DecState& d, uint32_t nbits, uint32_t& val) {
-    val = (uint32_t)(d.x & ((1u << nbits) - 1));
-    d.x >>= nbits;
-    return refill(d);
-}
-
-// rans_interface.cpp:231-281 (one symbol per index)
+// rans_interface.cpp:231-281 (one symbol per index); the per-symbol state machine is rans_decode.hpp's
 int decode_symbols(DecState& d, const int32_t* indexes, int64_t n, const cai_rans_tables* t, int32_t* out,
                    std::string& err) {
-    const char* trunc = "truncated or corrupt stream";
     for (int64_t i = 0; i < n; ++i) {
         const int32_t idx = indexes[i];
-        if (idx < 0 || idx >= t->n_cdfs) {
-            err = "cdf index " + std::to_string(idx) + " out of range";
-            return CAI_EINVAL;
+        switch (cai_rans::decode_symbol(d, idx, t->cdfs, t->cdf_stride, t->cdf_sizes, t->offsets, t->n_cdfs, out + i,
+                                        cai_rans::BinarySearch())) {
+            case cai_rans::kOk: break;
+            case cai_rans::kBadIndex: err = "cdf index " + std::to_string(idx) + " out of range"; return CAI_EINVAL;
+            case cai_rans::kBadCdfSize: err = "invalid cdf size for index " + std::to_string(idx); return CAI_EINVAL;
+            default: err = "truncated or corrupt stream"; return CAI_EINVAL;
         }
-        const int32_t* cdf = t->cdfs + (int64_t)idx * t->cdf_stride;
-        const int32_t size = t->cdf_sizes[idx];
-        const int32_t max_value = size - 2;
-        if (max_value < 0 || max_value + 1 >= t->cdf_stride) {
-            err = "invalid cdf size for index " + std::to_string(idx);
-            return CAI_EINVAL;
-        }
-        const uint32_t cum = (uint32_t)(d.x & ((1u << kScaleBits) - 1));
-        // first slot whose CDF value exceeds cum (the reference's linear
-        // find_if; a binary search on the non-decreasing table finds the same)
-        const int32_t* it = std::upper_bound(cdf, cdf + size, (int32_t)cum);
-        const int32_t s = (int32_t)(it - cdf) - 1;
-        if (s < 0 || s >= size - 1) {
-            err = trunc;
-            return CAI_EINVAL;
-        }
-        const uint64_t start = (uint32_t)cdf[s], freq = (uint32_t)(cdf[s + 1] - cdf[s]);
-        d.x = freq * (d.x >> kScaleBits) + (d.x & ((1u << kScaleBits) - 1)) - start;
-        if (!refill(d)) {
-            err = trunc;
-            return CAI_EINVAL;
-        }
-        int32_t value = s;
-        if (value == max_value) {
-            uint32_t val;
-            if (!get_bits(d, kBypassBits, val)) {
-                err = trunc;
-                return CAI_EINVAL;
-            }
-            int32_t n_bypass = (int32_t)val;
-            while (val == kMaxBypass) {
-                if (!get_bits(d, kBypassBits, val)) {
-                    err = trunc;
-                    return CAI_EINVAL;
-                }
-                n_bypass += (int32_t)val;
-            }
-            if (n_bypass > 8) {
-                err = trunc;
-                return CAI_EINVAL;
-            }
-            uint32_t raw_val = 0;
-            for (int32_t j = 0; j < n_bypass; ++j) {
-                if (!get_bits(d, kBypassBits, val)) {
-                    err = trunc;
-                    return CAI_EINVAL;
-                }
-                raw_val |= val << (j * kBypassBits);
-            }
-            value = (int32_t)(raw_val >> 1);
-            if (raw_val & 1)
-                value = -value - 1;
-            else
-                value += max_value;
-        }
-        out[i] = value + t->offsets[idx];
     }
     return CAI_OK;
 }

@@ -673,6 +673,63 @@ int cai_msssim_bwd(const float* x, const float* y, int32_t planes, int32_t H, in
                    void* stream);
 
 /* =======================================================================
+ * Fused autoregressive entropy coding of the context models (csrc/ar_coder.hip):
+ * google.py:565-608 / 654-692's per-pixel loop as one launch, one workgroup per image.
+ * ======================================================================= */
+/* All tensors fp32, dense, pixel-major: y, y_hat [B,H,W,M], params [B,H,W,Cp]; symbols / indexes / scales / means
+ * [B][H*W*M] in raster order (pixel-major, channel-minor: the order the serial path feeds the coder).
+ * The network is context conv (masked 5x5, M -> Cx) and three 1x1 layers C0 = Cp + Cx -> C1 -> C2 -> 2M with
+ * LeakyReLU(slope) after the first two, reading cat(params, ctx).  Packed weights are [K][pad4(O)] (input-major
+ * rows, zero columns past O), 16-byte aligned: w_ctx rows are tap-major (the 12 causal taps: rows -2, -1 left
+ * to right, then row 0's two left neighbours), channel-minor; w1p / w1c are the first layer's params / context
+ * halves.  Indexes follow GaussianConditional.build_indexes on scale_table[n_scales] clamped at scale_bound,
+ * symbols are rintf(y - mean), y_hat = float(symbol) + mean.  Results do not depend on B.
+ * encode: reads y; writes symbols, indexes, y_hat (and scales, means when non-NULL).
+ * decode: reads stream b from data[offsets[b] .. + lengths[b]) (device arrays; offsets multiples of 4) with the
+ * CDF tables (device, as cai_rans_tables), decoding what cai_rans_decode decodes; writes y_hat (and symbols,
+ * indexes, scales, means when non-NULL) and status[b] (device): 0, or 1 truncated / corrupt stream, 2 CDF index
+ * out of range, 3 invalid CDF size, 4 bad stream offset / length.  A failed stream stops there; reads never
+ * leave [data, data + data_bytes).  encode writes status[b] = 0 when status is non-NULL. */
+typedef struct cai_ar_args {
+    int32_t B, H, W, M;
+    int32_t Cp, Cx, C1, C2;
+    const float* y;
+    const float* params;
+    const float* w_ctx;
+    const float* b_ctx;
+    const float* w1p;
+    const float* w1c;
+    const float* b1;
+    const float* w2;
+    const float* b2;
+    const float* w3;
+    const float* b3;
+    float slope;
+    float scale_bound;
+    const float* scale_table;
+    int32_t n_scales;
+    int32_t cdf_stride;
+    float* y_hat;
+    int32_t* symbols;
+    int32_t* indexes;
+    float* scales;
+    float* means;
+    const uint8_t* data;
+    int64_t data_bytes;
+    const int64_t* offsets;
+    const int64_t* lengths;
+    const int32_t* cdfs;
+    const int32_t* cdf_sizes;
+    const int32_t* cdf_offsets;
+    int32_t n_cdfs;
+    int32_t* status;
+} cai_ar_args;
+/* workspace: the first layer's params half for every pixel (B*H*W*C1 floats); 0 = bad shape */
+size_t cai_ar_workspace_bytes(const cai_ar_args* args);
+int cai_ar_encode(const cai_ar_args* args, void* workspace, size_t ws_bytes, void* stream);
+int cai_ar_decode(const cai_ar_args* args, void* workspace, size_t ws_bytes, void* stream);
+
+/* =======================================================================
  * Optimiser over flat fp32 buffers (torch.optim.Adam semantics).
  * ======================================================================= */
 /* state[0] = sum(g^2) (fp32); workspace >= cai_reduce_workspace_bytes(n) */
