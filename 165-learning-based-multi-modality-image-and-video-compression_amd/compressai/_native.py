@@ -127,6 +127,10 @@ SIGNATURES = {
                           _P, _S, _P]),
     "cai_conv_fwd_res": (_I, [_G, _I, _P, c_int32, c_int32, _P, _P, c_int32, _F, _P, c_int32, _P, _I, _I64, _I64,
                               _I64, _I64, _P, _S, _P]),
+    "cai_conv_gdn_fwd": (_I, [_G, _I, _P, c_int32, c_int32, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, c_int32, _P,
+                              c_int32, _P, _S, _P]),
+    "cai_conv_gdn_fused": (c_int32, [_G, _I, c_int32]),
+    "cai_conv_gdn_kernel_name": (c_char_p, [_G, _I, c_int32, c_int32]),
     "cai_conv_dgrad": (_I, [_G, _I, _P, c_int32, _P, _P, c_int32, c_int32, _F, _P, c_int32, _P, _S, _P]),
     "cai_conv_dgrad_res": (_I, [_G, _I, _P, c_int32, _P, _P, c_int32, _P, c_int32, c_int32, _F, _P, c_int32, _P, _S,
                                 _P]),
@@ -155,6 +159,8 @@ SIGNATURES = {
     "cai_edge_pack_weights": (_I, [_G, _I, _I, _P, _P, _P]),
     "cai_edge_pack_describe": (_I, [_G, _I, _I, _P, _P, _P]),
     "cai_edge_conv_fwd": (_I, [_G, _P, _P, _P, _P, c_int32, _P]),
+    "cai_edge_conv_gdn_fwd": (_I, [_G, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int32, _P]),
+    "cai_edge_conv_gdn_fused": (c_int32, [_G]),
     "cai_edge_deconv_fwd": (_I, [_G, _P, c_int32, _P, _P, _P, _P]),
     "cai_edge_deconv_dgrad": (_I, [_G, _P, _P, _P, c_int32, _P]),
     "cai_edge_wgrad": (_I, [_G, _P, _P, c_int32, _P, _P, c_int32, _P, _S, _P]),
@@ -256,7 +262,8 @@ class _Lib:
         fn = self._bound(name)
 
         if fn.restype is c_int and name not in ("cai_version", "cai_abi_count", "cai_edge_supported",
-                                                "cai_conv_split_factor"):
+                                                "cai_conv_split_factor", "cai_conv_gdn_fused",
+                                                "cai_edge_conv_gdn_fused"):
             def call(*args):
                 rc = fn(*args)
                 if rc != CAI_OK:

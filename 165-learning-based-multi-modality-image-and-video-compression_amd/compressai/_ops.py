@@ -461,10 +461,11 @@ class ConvSpec:
     """Static description of one Conv2d / ConvTranspose2d call site."""
 
     __slots__ = ("k", "s", "p", "op", "transposed", "act", "act_param", "in_abs", "out_nchw32",
-                 "in_mask", "in_mask_param", "act_bwd_downstream")
+                 "in_mask", "in_mask_param", "act_bwd_downstream", "gdn")
 
     def __init__(self, k, s, p, op=0, transposed=False, act=ACT_NONE, act_param=0.0, in_abs=False,
-                 out_nchw32=False, in_mask=MASK_NONE, in_mask_param=0.0, act_bwd_downstream=False):
+                 out_nchw32=False, in_mask=MASK_NONE, in_mask_param=0.0, act_bwd_downstream=False, gdn=None):
+        self.gdn = gdn   # GdnEpilogue: the GDN that consumes this conv's output, run in the conv's launch if it can
         self.k, self.s, self.p, self.op = int(k), int(s), int(p), int(op)
         self.transposed = bool(transposed)
         self.act, self.act_param = int(act), float(act_param)
@@ -633,6 +634,50 @@ def residual_fusable(spec: ConvSpec) -> bool:
             and not spec.act_bwd_downstream and not spec.in_abs)
 
 
+# CAI_GDN_EPI=0 turns the forward GDN / IGDN fusion into the producing conv's kernels off (tests flip the flag)
+GDN_EPI = os.environ.get("CAI_GDN_EPI", "1") != "0"
+
+
+class GdnEpilogue:
+    """Links a conv call to the GDN / IGDN that consumes its output (layers/conv.py Sequential).  Where a kernel of
+    the conv can host the GDN forward (cai_conv_gdn_fused), ConvFn.forward launches cai_conv_gdn_fwd, which writes
+    the conv's output x and y = GDN(x), and leaves y and the reparametrised operands here; GdnFn.forward then takes
+    y as given and does not launch.  Autograd is unchanged: a ConvFn node and a GdnFn node saving what they always
+    save."""
+
+    __slots__ = ("beta_raw", "gamma_raw", "inverse", "beta_min", "reparam_offset", "y", "params")
+
+    def __init__(self, beta_raw, gamma_raw, inverse, beta_min, reparam_offset):
+        self.beta_raw, self.gamma_raw, self.inverse = beta_raw, gamma_raw, bool(inverse)
+        self.beta_min, self.reparam_offset = float(beta_min), float(reparam_offset)
+        self.y = self.params = None
+
+
+def _gdn_operands(beta_raw, gamma_raw, beta_min, reparam_offset, dt, device):
+    """(beta_raw fp32, gamma_raw fp32, beta, gamma_op) of a GDN layer: the reparametrisation of the model forward's
+    pack_many launch (_prepack.py) when there is one, else a cai_gdn_reparam launch."""
+    C = beta_raw.shape[0]
+    br = beta_raw.detach().float().contiguous()
+    gr = gamma_raw.detach().float().contiguous()
+    packer = _prepack_active()
+    pre = (packer.lookup(gamma_raw, dt, ("gdn", float(beta_min), float(reparam_offset)))
+           if packer is not None and gr.data_ptr() == gamma_raw.data_ptr() else None)
+    if pre is not None:
+        beta, gop = pre
+    else:
+        beta = torch.empty(C, dtype=torch.float32, device=device)
+        gop = torch.empty(2 * C * C, dtype=dt, device=device)
+        lib.cai_gdn_reparam(_p(br), _p(gr), C, beta_min, reparam_offset, dcode(dt), _p(beta), _p(gop), _stream())
+    return br, gr, beta, gop
+
+
+def _gdn_epilogue_ok(spec: ConvSpec, g: ConvGeom, dt, cout: int) -> bool:
+    epi = spec.gdn
+    return (epi is not None and GDN_EPI and dt == torch.bfloat16 and cout == 128 and spec.act == ACT_NONE
+            and not spec.out_nchw32 and tuple(epi.gamma_raw.shape) == (cout, cout)
+            and lib.cai_conv_gdn_fused(ctypes.byref(g), dcode(dt), int(spec.in_abs)) != 0)
+
+
 class ConvFn(torch.autograd.Function):
     """y = act(conv(x) + bias [+ res]).  ``res`` (optional, same shape as y) is the residual of ResidualUnit
     (layers.py:211-226: ``out += identity; relu(out)``) added in the conv epilogue before the activation; its
@@ -664,8 +709,25 @@ class ConvFn(torch.autograd.Function):
             y = empty_pm(B, cout, g.out_h, g.out_w, dt, x.device)
             frag = _edge_frag(g, dt, 0, weight)
             fl, nb = _ledger.conv_cost(g, _es(dt), 0, x_bytes=4)
-            _ledger.run(lambda: lib.cai_edge_conv_fwd(ctypes.byref(g), _p(x32), _p(frag), _p(b), _p(y), cout, _stream()),
-                        "conv_fwd", "edge_s2d_kernel (conv fwd)", fl, nb, dt, _ledger.shape_of(g))
+            epi = spec.gdn
+            if (epi is not None and GDN_EPI and dt == torch.bfloat16 and cout == 128 and spec.act == ACT_NONE
+                    and not epi.inverse and tuple(epi.gamma_raw.shape) == (cout, cout)
+                    and lib.cai_edge_conv_gdn_fused(ctypes.byref(g)) != 0):
+                # the GDN after this conv in the same launch (edge_s2d_kernel's GDN variant)
+                ops = _gdn_operands(epi.beta_raw, epi.gamma_raw, epi.beta_min, epi.reparam_offset, dt, x.device)
+                beta, gop = ops[2], ops[3]
+                y2 = empty_pm(B, cout, g.out_h, g.out_w, dt, x.device)
+                npix = B * g.out_h * g.out_w
+                fl += 2.0 * npix * cout * cout
+                nb += npix * cout * _es(dt) + cout * cout * _es(dt)
+                _ledger.run(lambda: lib.cai_edge_conv_gdn_fwd(ctypes.byref(g), _p(x32), _p(frag), _p(b), _p(y), cout,
+                                                              _p(gop), _p(beta), _p(y2), cout, _stream()),
+                            "conv_fwd", "edge_s2d_kernel (conv fwd)", fl, nb, dt, _ledger.shape_of(g) + " +GDN")
+                epi.y, epi.params = y2, ops
+            else:
+                _ledger.run(lambda: lib.cai_edge_conv_fwd(ctypes.byref(g), _p(x32), _p(frag), _p(b), _p(y), cout,
+                                                          _stream()),
+                            "conv_fwd", "edge_s2d_kernel (conv fwd)", fl, nb, dt, _ledger.shape_of(g))
             ctx.xld = 0
             ctx.save_for_backward(x32, weight, None)
             return y
@@ -720,10 +782,27 @@ class ConvFn(torch.autograd.Function):
                 wp = _pack_weight(g, dt, 0, weight)
             ws, wsb = _conv_ws(g, dt, 0, x.device)
             fl, nb = _ledger.conv_cost(g, _es(dt), 0, y_bytes=4 if spec.out_nchw32 else None)
-            _ledger.run(lambda: lib.cai_conv_fwd(ctypes.byref(g), dcode(dt), _p(xpm), xld, int(spec.in_abs), _p(wp),
-                                                 _p(b), spec.act, spec.act_param, _p(y), ydt, *ys, _p(ws), wsb,
-                                                 _stream()),
-                        "conv_fwd", _conv_kernel(g, dt, 0, spec.in_abs), fl, nb, dt, _ledger.shape_of(g))
+            if _gdn_epilogue_ok(spec, g, dt, cout):
+                # the GDN after this conv in the same launch: the conv's output and y = GDN(output)
+                epi = spec.gdn
+                ops = _gdn_operands(epi.beta_raw, epi.gamma_raw, epi.beta_min, epi.reparam_offset, dt, x.device)
+                beta, gop = ops[2], ops[3]
+                y2 = empty_pm(B, cout, g.out_h, g.out_w, dt, x.device)
+                npix = B * g.out_h * g.out_w
+                # the conv's work plus the GDN's, minus the read of x that the fusion removes
+                fl += 2.0 * npix * cout * cout
+                nb += npix * cout * _es(dt) + cout * cout * _es(dt)
+                _ledger.run(lambda: lib.cai_conv_gdn_fwd(ctypes.byref(g), dcode(dt), _p(xpm), xld, int(spec.in_abs),
+                                                         _p(wp), _p(b), _p(y), *ys, _p(gop), _p(beta),
+                                                         int(epi.inverse), _p(y2), cout, _p(ws), wsb, _stream()),
+                            "conv_fwd", _conv_kernel(g, dt, 0, spec.in_abs), fl, nb, dt,
+                            _ledger.shape_of(g) + (" +IGDN" if epi.inverse else " +GDN"))
+                epi.y, epi.params = y2, ops
+            else:
+                _ledger.run(lambda: lib.cai_conv_fwd(ctypes.byref(g), dcode(dt), _p(xpm), xld, int(spec.in_abs),
+                                                     _p(wp), _p(b), spec.act, spec.act_param, _p(y), ydt, *ys, _p(ws),
+                                                     wsb, _stream()),
+                            "conv_fwd", _conv_kernel(g, dt, 0, spec.in_abs), fl, nb, dt, _ledger.shape_of(g))
         ctx.xld = xld
         ctx.save_for_backward(xpm, weight, y if spec.act != ACT_NONE else None)
         return y
@@ -1417,7 +1496,7 @@ class AttentionBlockFn(torch.autograd.Function):
 
 class GdnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, beta_raw, gamma_raw, inverse: bool, beta_min: float, reparam_offset: float):
+    def forward(ctx, x, beta_raw, gamma_raw, inverse: bool, beta_min: float, reparam_offset: float, epi=None):
         _check_cuda(x, beta_raw, gamma_raw)
         dt = compute_dtype()
         code = dcode(dt)
@@ -1425,22 +1504,17 @@ class GdnFn(torch.autograd.Function):
         xpm, xld = to_pm(x, dt, 8)
         npix = B * H * W
         st = _stream()
-        br = beta_raw.detach().float().contiguous()
-        gr = gamma_raw.detach().float().contiguous()
-        # the model forward's pack_many launch has reparametrised this layer already (_prepack.py)
-        packer = _prepack_active()
-        pre = (packer.lookup(gamma_raw, dt, ("gdn", float(beta_min), float(reparam_offset)))
-               if packer is not None and gr.data_ptr() == gamma_raw.data_ptr() else None)
-        if pre is not None:
-            beta, gop = pre
+        if epi is not None and epi.y is not None:
+            # the conv that produced x has run this layer in its own launch (GdnEpilogue): y is given
+            br, gr, beta, gop = epi.params
+            y = epi.y
+            epi.y = epi.params = None
         else:
-            beta = torch.empty(C, dtype=torch.float32, device=x.device)
-            gop = torch.empty(2 * C * C, dtype=dt, device=x.device)
-            lib.cai_gdn_reparam(_p(br), _p(gr), C, beta_min, reparam_offset, code, _p(beta), _p(gop), st)
-        y = empty_pm(B, C, H, W, dt, x.device)
-        _ledger.run(lambda: lib.cai_gdn_fwd(code, _p(xpm), xld, npix, C, _p(gop), _p(beta), int(inverse), _p(y), C, st),
-                    "gdn_fwd", lambda: _gdn_name(code, npix, C, xld, 0), 2.0 * npix * C * C, 2 * npix * C * _es(dt) + C * C * _es(dt), dt,
-                    f"{'IGDN' if inverse else 'GDN'} C={C} npix={npix}")
+            br, gr, beta, gop = _gdn_operands(beta_raw, gamma_raw, beta_min, reparam_offset, dt, x.device)
+            y = empty_pm(B, C, H, W, dt, x.device)
+            _ledger.run(lambda: lib.cai_gdn_fwd(code, _p(xpm), xld, npix, C, _p(gop), _p(beta), int(inverse), _p(y), C, st),
+                        "gdn_fwd", lambda: _gdn_name(code, npix, C, xld, 0), 2.0 * npix * C * C, 2 * npix * C * _es(dt) + C * C * _es(dt), dt,
+                        f"{'IGDN' if inverse else 'GDN'} C={C} npix={npix}")
         ctx.save_for_backward(xpm, br, gr, beta, gop)
         ctx.cfg = (dt, xld, int(inverse), float(beta_min), float(reparam_offset))
         ctx.params = (beta_raw, gamma_raw)
@@ -1490,7 +1564,7 @@ class GdnFn(torch.autograd.Function):
                         3 * npix * C * _es(dt) + 8 * C * C, dt, f"{'IGDN' if inverse else 'GDN'} C={C} npix={npix}")
         if direct:
             dbr = dgr = None
-        return dx, dbr, dgr, None, None, None
+        return dx, dbr, dgr, None, None, None, None
 
 
 class Gdn1OutFn(torch.autograd.Function):

@@ -8,8 +8,11 @@ them).  ``forward`` runs ConvFn (cai_conv_fwd / _dgrad / _wgrad).
 ``Sequential`` fuses ``conv -> ReLU/LeakyReLU`` pairs: the activation runs in
 the conv epilogue, and when the activated tensor feeds the next conv its
 backward mask is applied in that conv's dgrad epilogue (MASK_POS/LEAKY) -- no
-separate elementwise kernels.  Indices (and so state_dict keys such as
-``h_a.2.weight``) are those of the reference Sequentials.
+separate elementwise kernels.  A ``conv -> GDN`` pair is linked the same way:
+where one of the conv's kernels can run the GDN forward (bf16, 128 channels),
+the conv's launch writes both tensors and the GDN launches nothing
+(``_ops.GdnEpilogue``; ``CAI_GDN_EPI=0`` turns it off).  Indices (and so
+state_dict keys such as ``h_a.2.weight``) are those of the reference Sequentials.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import torch.nn as nn
 
 from .._native import ACT_LEAKY, ACT_NONE, ACT_RELU, MASK_LEAKY, MASK_NONE, MASK_POS, MASK_SIGN
 from .._ops import ActFn, ConvFn, ConvSpec, PixelShuffleFn
+from .gdn import GDN
 
 
 def _square(v, name):
@@ -30,7 +34,7 @@ def _square(v, name):
 
 class _ConvMixin:
     def _spec(self, act=ACT_NONE, act_param=0.0, in_abs=False, in_mask=MASK_NONE, in_mask_param=0.0,
-              act_bwd_downstream=False, out_channels=None):
+              act_bwd_downstream=False, out_channels=None, gdn=None):
         if self.groups != 1 or _square(self.dilation, "dilation") != 1:
             raise ValueError("groups/dilation other than 1 are not supported")
         if self.padding_mode != "zeros":
@@ -41,7 +45,7 @@ class _ConvMixin:
         return ConvSpec(_square(self.kernel_size, "kernel_size"), _square(self.stride, "stride"),
                         _square(self.padding, "padding"), op, transposed, act, act_param, in_abs,
                         out_nchw32=(cout % 8 != 0), in_mask=in_mask, in_mask_param=in_mask_param,
-                        act_bwd_downstream=act_bwd_downstream)
+                        act_bwd_downstream=act_bwd_downstream, gdn=gdn)
 
     def run(self, x, res=None, **kw):
         if res is not None:   # y = act(conv(x) + bias + res) in the epilogue (ResidualUnit)
@@ -101,6 +105,7 @@ class Sequential(nn.Sequential):
         i = 0
         pending = (MASK_SIGN, 0.0) if input_abs else (in_mask, in_mask_param)
         first = True
+        epi = None          # the GdnEpilogue handed to the conv before a GDN child (None: not linked)
         cuts = self.__dict__.get("_cut_fns")
         while i < n:
             m = mods[i]
@@ -123,6 +128,13 @@ class Sequential(nn.Sequential):
                     downstream = a != ACT_NONE and (isinstance(after, _CONVS) or _is_subpel(after))
                 kw = dict(act=a, act_param=prm, in_mask=pending[0], in_mask_param=pending[1],
                           act_bwd_downstream=downstream)
+                # conv -> GDN: the GDN forward runs in the conv's launch where a kernel hosts it (_ops.GdnEpilogue);
+                # training mode with gradients enabled only (evaluation paths launch what they always did), and not
+                # across a gradient-bucket cut at the GDN's input
+                if (isinstance(m, _CONVS) and a == ACT_NONE and type(after) is GDN and self.training
+                        and torch.is_grad_enabled() and not (cuts and i + 1 in cuts)):
+                    epi = after.epilogue()
+                    kw["gdn"] = epi
                 if isinstance(m, _CONVS):
                     x = m.run(x, in_abs=(input_abs and first), **kw)
                 else:
@@ -133,7 +145,10 @@ class Sequential(nn.Sequential):
                 if input_abs and first:
                     x = torch.abs(x)
                 a, prm = _act_of(m)
-                x = ActFn.apply(x, a, prm) if a != ACT_NONE else m(x)
+                if epi is not None and type(m) is GDN:
+                    x, epi = m(x, epi), None
+                else:
+                    x = ActFn.apply(x, a, prm) if a != ACT_NONE else m(x)
                 pending = (MASK_NONE, 0.0)
                 i += 1
             first = False

@@ -9,7 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .._native import MASK_SIGN
-from .._ops import ConvFn, ConvSpec, Gdn1OutFn, GdnFn, compute_dtype
+from .._ops import ConvFn, ConvSpec, Gdn1OutFn, GdnEpilogue, GdnFn, compute_dtype
 from ..ops.parametrizers import NonNegativeParametrizer
 
 __all__ = ["GDN", "GDN1"]
@@ -24,12 +24,19 @@ class GDN(nn.Module):
         self.gamma_reparam = NonNegativeParametrizer()
         self.gamma = nn.Parameter(self.gamma_reparam.init(float(gamma_init) * torch.eye(in_channels)))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def epilogue(self) -> GdnEpilogue:
+        """This layer as the epilogue of the conv that feeds it (layers/conv.py Sequential)."""
+        return GdnEpilogue(self.beta, self.gamma, self.inverse, self.beta_reparam.minimum,
+                           self.beta_reparam.reparam_offset)
+
+    def forward(self, x: torch.Tensor, epi: GdnEpilogue = None) -> torch.Tensor:
         C = x.shape[1]
         cap = 256 if compute_dtype() == torch.bfloat16 else 192
         if C % 32 == 0 and C <= cap:
             return GdnFn.apply(x, self.beta, self.gamma, self.inverse, self.beta_reparam.minimum,
-                               self.beta_reparam.reparam_offset)
+                               self.beta_reparam.reparam_offset, epi)
+        if epi is not None and epi.y is not None:
+            raise RuntimeError("GDN: a fused conv epilogue ran for a channel count that takes the padded path")
         # the kernels take channel counts that are multiples of 32 (MFMA K = 32 bf16): pad with zero
         # channels, gamma rows / columns of 0 and beta of 1 -- the real channels' norm is unchanged and the
         # padded outputs (0) are sliced off; autograd routes the gradients back through the padding

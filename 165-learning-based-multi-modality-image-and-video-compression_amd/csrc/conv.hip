@@ -28,6 +28,7 @@
 
 #include <type_traits>
 #include "edge_frag.hpp"
+#include "gdn_tile.hpp"
 #include "mfma.hpp"
 #include "reduce_jobs.hpp"
 #include "conv_args.hpp"
@@ -1049,6 +1050,110 @@ __host__ __device__ constexpr int halo_younger_sp(int t, int nstb, int npi, int 
 }
 
 
+// The plain branch of conv_epilogue_rows_t (bias only, bf16 pixel-major output, no split) followed by the forward
+// GDN / IGDN of the tile (cai_conv_gdn_fwd): 256 tile rows x 128 channels on 8 waves.  Each lane stores its bf16 x
+// to a.y as the plain branch does and into an LDS tile [256 px][128 ch] (rows padded by 16 bytes as in stage_mats);
+// gamma is staged beside it.  After one barrier wave w runs pixel tiles 4 (w >> 1) .. +4 against output blocks
+// 4 (w & 1) .. +4 with the lane-local step of gdn_tile.hpp (x^2 chunks read from the LDS tile in the canonical B
+// layout) and writes y as 16-byte chunks.  Rows outside the image are stored nowhere and enter the GDN as zeros.
+// Every global load (bias, beta, gamma) is retired before the first store.  smem must hold
+// GdnEpiLds::BYTES.
+struct GdnEpiLds {
+    static constexpr int C = 128, RS = 2 * C + 16;
+    static constexpr int X = 0, G = 256 * RS, B = G + C * RS, BYTES = B + C * 4;
+};
+
+template <int BM, int BN, int WM, int WN, bool INV, class RowMap>
+__device__ __forceinline__ void conv_epilogue_gdn_t(const ConvArgs& a, const GdnEpi& ge, const PhaseDesc& P, int plane,
+                                                    char* smem, const f32x4 (&acc)[BM / WM / 16][BN / WN / 16],
+                                                    RowMap rowm) {
+    static_assert(BM == 256 && BN == 128 && WM == 4 && WN == 2, "GDN epilogue tile");
+    constexpr int C = GdnEpiLds::C, KB = C / 32, RS = GdnEpiLds::RS;
+    constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid / WN, wn = wid % WN;
+    const int g_ = lane >> 4, i16 = lane & 15;
+    char* const Lx = smem + GdnEpiLds::X;
+    char* const Lg = smem + GdnEpiLds::G;
+    float* const Lb = reinterpret_cast<float*>(smem + GdnEpiLds::B);
+
+    // loads: bias, beta, gamma (C * C * 2 / 16 = 2048 chunks on 512 threads)
+    f32x4 bv[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+        const int n = wn * WTN + tn * 16 + 4 * g_;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bv[tn][r] = a.bias ? a.bias[n + r] : 0.f;
+    }
+    constexpr int CH = 2 * C / 16, NG = C * CH / 512;
+    u32x4 gs[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int id = tid + 512 * i, row = id / CH, ch = id - row * CH;
+        gs[i] = *reinterpret_cast<const u32x4*>(ge.gamma + row * C + ch * 8);
+    }
+    const float bt = tid < C ? ge.beta[tid] : 0.f;
+    wait_vmcnt<0>();
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int id = tid + 512 * i, row = id / CH, ch = id - row * CH;
+        *reinterpret_cast<u32x4*>(Lg + row * RS + ch * 16) = gs[i];
+    }
+    if (tid < C) Lb[tid] = bt;
+
+    // x: to global as the plain branch, and to the LDS tile
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+        const int row = wm * WTM + tm * 16 + i16;
+        const int m = rowm(row);
+        int b, oy, ox;
+        out_pixel<bf16>(a, P, plane, m < 0 ? 0 : m, b, oy, ox);
+        bf16* Y = reinterpret_cast<bf16*>(a.y) + (int64_t)b * a.ysb + (int64_t)oy * a.ysy + (int64_t)ox * a.ysx;
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const int n = wn * WTN + tn * 16 + 4 * g_;
+            bf16x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[r] = (bf16)(acc[tm][tn][r] + bv[tn][r]);
+            if (m >= 0) *reinterpret_cast<bf16x4*>(Y + n) = h;
+            *reinterpret_cast<bf16x4*>(Lx + row * RS + n * 2) = m >= 0 ? h : bf16x4{};
+        }
+    }
+    __syncthreads();
+
+    // GDN: pixel tiles 4 pg .. +4, output chunks 2 hf, 2 hf + 1 (output blocks 4 hf .. +4)
+    const int pg = wid >> 1, hf = wid & 1;
+    u32x4 ga[4][KB];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        const char* grow = Lg + perm_ch(4 * hf + cb, i16) * RS + 16 * g_;
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) ga[cb][kb] = *reinterpret_cast<const u32x4*>(grow + 64 * kb);
+    }
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) {
+        const int row = pg * 64 + tt * 16 + i16;
+        u32x4 xq[KB], q[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            xq[kb] = *reinterpret_cast<const u32x4*>(Lx + row * RS + (32 * kb + 8 * g_) * 2);
+            q[kb] = sq_chunk<bf16>(xq[kb]);
+        }
+        u32x4 xc[2], yv[2];
+        xc[0] = hf ? xq[2] : xq[0];
+        xc[1] = hf ? xq[3] : xq[1];
+        gdn_tile_fwd_part<C, INV, false, 2>(ga, Lb, xc, q, yv, g_, 2 * hf);
+        const int m = rowm(row);
+        if (m >= 0) {
+            int b, oy, ox;
+            out_pixel<bf16>(a, P, plane, m, b, oy, ox);
+            bf16* Y2 = ge.y + (((int64_t)b * a.out_h + oy) * a.out_w + ox) * ge.y_ld + 64 * hf + 8 * g_;
+            *reinterpret_cast<u32x4*>(Y2) = yv[0];
+            *reinterpret_cast<u32x4*>(Y2 + 32) = yv[1];
+        }
+    }
+}
+
 // transposed accumulators + register-direct epilogue (conv_epilogue_rows_t) in the halo kernels: the
 // phase kernel's launches 57.8 vs 59.7 us average in the C2 step (profiles/r02_edge_s2d_ab.log, r02af)
 
@@ -1073,8 +1178,12 @@ struct HaloCfg {
     static constexpr int BYTES = (PATCH + NSTB * BSTAGE > EPI) ? PATCH + NSTB * BSTAGE : EPI;
 };
 
-template <int KS>
-__global__ __launch_bounds__(512, 1) void conv_halo_kernel(const ConvArgs a, int tiles_x, int tiles_y) {
+// GDN: 0 = the conv alone; 1 / 2 = the forward GDN / IGDN of the output in the epilogue (conv_epilogue_gdn_t; no
+// split-K) with one more kernel argument, the GdnEpi.  The fused form is an instantiation of its own with this
+// kernel's text: conv_halo_kernel<KS, 0> compiles to the code the kernel had before it took the parameter.
+template <int KS, int GDN = 0, typename... GE>
+__global__ __launch_bounds__(512, 1) void conv_halo_kernel(const ConvArgs a, int tiles_x, int tiles_y, const GE... ge) {
+    static_assert(sizeof...(GE) == (GDN != 0 ? 1 : 0), "one GdnEpi argument for the GDN forms");
     using H = HaloCfg<KS>;
     constexpr int BM = H::BM, BN = H::BN, WM = H::WM, WN = H::WN;
     constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
@@ -1253,8 +1362,13 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(const ConvArgs a, int
         const int oy = ty0 + row / H::TW, ox = tx0 + row % H::TW;
         return (oy < P.OHg && ox < P.OWg) ? b * plane + oy * P.OWg + ox : -1;
     };
-    conv_epilogue_rows_t<bf16, BM, BN, WM, WN, 512, decltype(rowm), false, false>(
-        a, P, plane, 0, reinterpret_cast<float*>(smem), acc, rowm, (int)blockIdx.z);
+    if constexpr (GDN != 0) {
+        static_assert(GdnEpiLds::BYTES <= H::BYTES, "GDN epilogue LDS");
+        conv_epilogue_gdn_t<BM, BN, WM, WN, GDN == 2>(a, (ge, ...), P, plane, smem, acc, rowm);
+    } else {
+        conv_epilogue_rows_t<bf16, BM, BN, WM, WN, 512, decltype(rowm), false, false>(
+            a, P, plane, 0, reinterpret_cast<float*>(smem), acc, rowm, (int)blockIdx.z);
+    }
 }
 
 // Halo-staged s^2-phase implicit GEMM for the stride-2 k5 transposed convolutions (ConvTranspose2d k5 s2 p2
@@ -1298,9 +1412,11 @@ struct HaloPhCfg {
 // NA-1 / NC-1 before dy0 / dx0).  GATHER = true: a stride-1 gather convolution (Conv2d k3 s1 forward): tap
 // (ty, tx) = kernel (kh, kw) reads cell (ty, tx) from the origin dy0 = -pad.  n0: the tile's first output
 // channel (grid y).
-template <int NA, int NC, int BN_ = 128, bool GATHER = false, bool MPF = false>
+// GDN / ge: as in conv_halo_body (BN_ = 128, one channel tile, no split)
+template <int NA, int NC, int BN_ = 128, bool GATHER = false, bool MPF = false, int GDN = 0>
 __device__ __forceinline__ void conv_halo_phase_body(const ConvArgs& a, char* smem, int ph, int split, int bid,
-                                                     int tiles_x, int tiles_y, int n0 = 0) {
+                                                     int tiles_x, int tiles_y, int n0 = 0,
+                                                     const GdnEpi* ge = nullptr) {
     using H = HaloPhCfg<NA, NC, BN_>;
     constexpr int BM = H::BM, BN = H::BN, WM = H::WM, WN = H::WN, DPS = H::DPS, NT = H::NT;
     constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
@@ -1465,8 +1581,13 @@ __device__ __forceinline__ void conv_halo_phase_body(const ConvArgs& a, char* sm
         const int oy = ty0 + row / H::TW, ox = tx0 + row % H::TW;
         return (oy < P.OHg && ox < P.OWg) ? b * plane + oy * P.OWg + ox : -1;
     };
-    conv_epilogue_rows_t<bf16, BM, BN, WM, WN, NT, decltype(rowm), (BN > 128), false, MPF>(
-        a, P, plane, n0, reinterpret_cast<float*>(smem), acc, rowm, ph * a.ksplit + split);
+    if constexpr (GDN != 0) {
+        static_assert(BN == 128 && GdnEpiLds::BYTES <= H::BYTES, "GDN epilogue LDS");
+        conv_epilogue_gdn_t<BM, BN, WM, WN, GDN == 2>(a, *ge, P, plane, smem, acc, rowm);
+    } else {
+        conv_epilogue_rows_t<bf16, BM, BN, WM, WN, NT, decltype(rowm), (BN > 128), false, MPF>(
+            a, P, plane, n0, reinterpret_cast<float*>(smem), acc, rowm, ph * a.ksplit + split);
+    }
 }
 
 
@@ -1687,6 +1808,26 @@ __global__ __launch_bounds__(512, 1) void conv_halo_phase_kernel(const ConvArgs 
     }
 }
 
+// conv_halo_phase_kernel<128> with the forward GDN (INV: IGDN) of its output in the epilogue; one channel tile,
+// no split-K
+template <bool INV>
+__global__ __launch_bounds__(512, 1) void conv_halo_phase_gdn_kernel(const ConvArgs a, int tiles_x, int tiles_y,
+                                                                     const GdnEpi ge) {
+    constexpr int BYTES = HaloPhCfg<3, 3>::BYTES > HaloPhCfg<2, 2>::BYTES ? HaloPhCfg<3, 3>::BYTES : HaloPhCfg<2, 2>::BYTES;
+    static_assert(BYTES >= HaloPhCfg<3, 2>::BYTES && BYTES >= HaloPhCfg<2, 3>::BYTES, "halo phase LDS");
+    __shared__ __attribute__((aligned(16))) char smem[BYTES];
+    constexpr int GDN = INV ? 2 : 1;
+    const int nt = gridDim.x >> 2;
+    const int ph = blockIdx.x / nt;
+    const int t = blockIdx.x - ph * nt;
+    const int bid = (nt & 7) == 0 ? (t & 7) * (nt >> 3) + (t >> 3) : t;
+    switch (ph) {
+        case 0: conv_halo_phase_body<3, 3, 128, false, false, GDN>(a, smem, 0, 0, bid, tiles_x, tiles_y, 0, &ge); break;
+        case 1: conv_halo_phase_body<3, 2, 128, false, false, GDN>(a, smem, 1, 0, bid, tiles_x, tiles_y, 0, &ge); break;
+        case 2: conv_halo_phase_body<2, 3, 128, false, false, GDN>(a, smem, 2, 0, bid, tiles_x, tiles_y, 0, &ge); break;
+        default: conv_halo_phase_body<2, 2, 128, false, false, GDN>(a, smem, 3, 0, bid, tiles_x, tiles_y, 0, &ge); break;
+    }
+}
 
 // Halo-staged stride-1 k3 p1 convolution (the 3x3 convs of cheng2020's residual / attention blocks and
 // sub-pixel convs, conv3x3 layers/layers.py:38-49 / 86-91): the phase body with one phase of 3x3 taps.
@@ -1759,6 +1900,109 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (n + e < a.Cout) store_out_scalar<T>(a, P, plane, m, n + e, v[e]);
+        }
+    }
+}
+
+// The split-K reduce with the forward GDN / IGDN of the conv's output in the same launch (cai_conv_gdn_fwd: bf16,
+// 128 output channels, pixel-major output, bias only).  In effect gdn_fwd_lane_kernel with another loader and one
+// more store: a wave owns 16 rows of a phase at a time and sums the ksplit fp32 partials of its lanes' channels
+// (32 kb + 8 (lane >> 4) .. +8 of row lane & 15) in split order -- the order and arithmetic of
+// conv_splitk_reduce_kernel, so x is bit-identical to that kernel's -- adds the bias, rounds to bf16, stores x,
+// runs the lane-local GDN step (gdn_tile.hpp) and stores y.  tiles_pp: 16-row tiles per phase (of ws_rows rows).
+// Registers: 256 VGPRs + 134 AGPRs, one wave per SIMD (which is all the grid asks for: one block per CU) -- the 128
+// registers of gamma fragments and the 128 of a batch's loads in flight do not fit 256 together, so the compiler
+// parks fragments in AGPRs and copies them back for the MFMAs; there is no room left for more loads in flight.
+template <bool INV>
+__global__ __launch_bounds__(256) void conv_splitk_reduce_gdn_kernel(const ConvArgs a, const GdnEpi ge, int tiles_pp) {
+    constexpr int C = 128, KB = C / 32, NB = C / 16;
+    __shared__ __attribute__((aligned(16))) char Lg[C * (2 * C + 16)];
+    __shared__ __attribute__((aligned(16))) float Lb[C];
+    __shared__ __attribute__((aligned(16))) float Lbias[C];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, p = lane & 15;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        Lb[c] = ge.beta[c];
+        Lbias[c] = a.bias ? a.bias[c] : 0.f;
+    }
+    stage_mats<C, 1, 256>(Lg, ge.gamma);
+    u32x4 ga[NB][KB];
+    afrag_lds<C>(ga, Lg, p, g);
+
+    const int64_t slab = (int64_t)a.ws_rows * a.ws_ld;
+    const int ntiles = a.nphase * tiles_pp;
+    for (int t = blockIdx.x * 4 + wave; t < ntiles; t += gridDim.x * 4) {
+        const int ph = t / tiles_pp;
+        const PhaseDesc P = ph == 0 ? a.ph[0] : (ph == 1 ? a.ph[1] : (ph == 2 ? a.ph[2] : a.ph[3]));
+        const int plane = P.OHg * P.OWg;
+        const int m = (t - ph * tiles_pp) * 16 + p;
+        const bool ok = m < a.B * plane;
+        const float* src = a.ws + ((int64_t)ph * a.ksplit) * slab + (int64_t)(ok ? m : 0) * a.ws_ld + 8 * g;
+        float v[KB][8];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[kb][e] = 0.f;
+        // split order fixed; loads in batches of 4 splits
+        int s = 0;
+        for (; s + 4 <= a.ksplit; s += 4) {
+            f32x4 lo[4][KB], hi[4][KB];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int kb = 0; kb < KB; ++kb) {
+                    lo[j][kb] = *reinterpret_cast<const f32x4*>(src + (s + j) * slab + 32 * kb);
+                    hi[j][kb] = *reinterpret_cast<const f32x4*>(src + (s + j) * slab + 32 * kb + 4);
+                }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[kb][e] += lo[j][kb][e];
+                        v[kb][4 + e] += hi[j][kb][e];
+                    }
+        }
+        for (; s < a.ksplit; ++s) {
+            f32x4 lo[KB], hi[KB];
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) {
+                lo[kb] = *reinterpret_cast<const f32x4*>(src + s * slab + 32 * kb);
+                hi[kb] = *reinterpret_cast<const f32x4*>(src + s * slab + 32 * kb + 4);
+            }
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[kb][e] += lo[kb][e];
+                    v[kb][4 + e] += hi[kb][e];
+                }
+        }
+        u32x4 xc[KB], q[KB], yv[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(Lbias + 32 * kb + 8 * g);
+            const f32x4 b1 = *reinterpret_cast<const f32x4*>(Lbias + 32 * kb + 8 * g + 4);
+            bf16x8 h;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                h[e] = (bf16)(v[kb][e] + b0[e]);
+                h[4 + e] = (bf16)(v[kb][4 + e] + b1[e]);
+            }
+            xc[kb] = __builtin_bit_cast(u32x4, h);
+            q[kb] = sq_chunk<bf16>(xc[kb]);
+        }
+        gdn_tile_fwd<C, INV, false>(ga, Lb, xc, q, yv, g);
+        if (ok) {
+            int b, oy, ox;
+            out_pixel<bf16>(a, P, plane, m, b, oy, ox);
+            bf16* X = reinterpret_cast<bf16*>(a.y) + (int64_t)b * a.ysb + (int64_t)oy * a.ysy + (int64_t)ox * a.ysx + 8 * g;
+            bf16* Y = ge.y + (((int64_t)b * a.out_h + oy) * a.out_w + ox) * ge.y_ld + 8 * g;
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) *reinterpret_cast<u32x4*>(X + 32 * kb) = xc[kb];
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) *reinterpret_cast<u32x4*>(Y + 32 * kb) = yv[kb];
         }
     }
 }
@@ -3866,49 +4110,85 @@ static ConvLaunch conv_launch(const cai_conv_geom* g, int dtype, int direction, 
     return L;
 }
 
+// A forward GDN / IGDN fused into the conv call (cai_conv_gdn_fwd) and the kernel that hosts it
+enum { GDN_HOST_NONE = 0, GDN_HOST_HALO, GDN_HOST_PHASE, GDN_HOST_REDUCE };
+struct GdnCall {
+    GdnEpi e;
+    int inverse;
+};
+
+// the host of a forward GDN after this conv call: the split-K reduce of any split launch, else the epilogue of
+// conv_halo_kernel<5> / conv_halo_phase_kernel<128> (quad: the four-phase kernel takes the call -- no host)
+static int gdn_host(const ConvLaunch& L, int dtype, int cout, bool quad) {
+    if (dtype != CAI_BF16 || cout != 128 || L.small) return GDN_HOST_NONE;
+    if (L.ksplit > 1) return L.ws_ld >= 128 ? GDN_HOST_REDUCE : GDN_HOST_NONE;
+    if (L.halo == 5) return GDN_HOST_HALO;
+    if (L.halo_ph && L.hbn == 128 && L.ntiles == 1 && !quad) return GDN_HOST_PHASE;
+    return GDN_HOST_NONE;
+}
+
+// the reduce launch of a split call (nothing without a split): gc = with the forward GDN of the output
+template <typename T>
+static void launch_splitk_reduce(const ConvArgs& a, const ConvLaunch& L, const GdnCall* gc, hipStream_t st) {
+    if (a.ksplit <= 1) return;
+    if (gc) {
+        const int tiles_pp = (L.mmax + 15) / 16;
+        const int grid = std::max(1, std::min(256, (a.nphase * tiles_pp + 3) / 4));
+        if (gc->inverse)
+            hipLaunchKernelGGL(conv_splitk_reduce_gdn_kernel<true>, dim3(grid), dim3(256), 0, st, a, gc->e, tiles_pp);
+        else
+            hipLaunchKernelGGL(conv_splitk_reduce_gdn_kernel<false>, dim3(grid), dim3(256), 0, st, a, gc->e, tiles_pp);
+        return;
+    }
+    const int VO = (a.y_vec && a.y_dtype == CAI_BF16) ? 8 : 4;
+    const int64_t total = (int64_t)L.mmax * ((a.Cout + VO - 1) / VO);
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (total + 255) / 256));
+    hipLaunchKernelGGL((conv_splitk_reduce_kernel<T>), dim3(gx, a.nphase), dim3(256), 0, st, a);
+}
+
 template <typename T, typename C>
-static void launch_conv(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
+static void launch_conv(const ConvArgs& a, const ConvLaunch& L, hipStream_t st, const GdnCall* gc = nullptr) {
     dim3 grid(L.mtiles, L.ntiles, a.nphase * a.ksplit);
     hipLaunchKernelGGL((conv_gemm_kernel<T, C>), grid, dim3(NT), 0, st, a);
-    if (a.ksplit > 1) {
-        const int VO = (a.y_vec && a.y_dtype == CAI_BF16) ? 8 : 4;
-        const int64_t total = (int64_t)L.mmax * ((a.Cout + VO - 1) / VO);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (total + 255) / 256));
-        hipLaunchKernelGGL((conv_splitk_reduce_kernel<T>), dim3(gx, a.nphase), dim3(256), 0, st, a);
-    }
+    launch_splitk_reduce<T>(a, L, gc, st);
 }
 
 template <typename C>
-static void launch_conv_glds(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
+static void launch_conv_glds(const ConvArgs& a, const ConvLaunch& L, hipStream_t st, const GdnCall* gc = nullptr) {
     dim3 grid(L.mtiles, L.ntiles, a.nphase * a.ksplit);
     hipLaunchKernelGGL((conv_glds_kernel<C>), grid, dim3(512), 0, st, a);
-    if (a.ksplit > 1) {
-        const int VO = (a.y_vec && a.y_dtype == CAI_BF16) ? 8 : 4;
-        const int64_t total = (int64_t)L.mmax * ((a.Cout + VO - 1) / VO);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (total + 255) / 256));
-        hipLaunchKernelGGL((conv_splitk_reduce_kernel<bf16>), dim3(gx, a.nphase), dim3(256), 0, st, a);
-    }
+    launch_splitk_reduce<bf16>(a, L, gc, st);
 }
 
-static void launch_conv_halo(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
+static void launch_conv_halo(const ConvArgs& a, const ConvLaunch& L, hipStream_t st, const GdnCall* gc = nullptr) {
     dim3 grid(L.mtiles, 1, a.ksplit);
+    if (gc && a.ksplit == 1) {    // GDN_HOST_HALO
+        if (gc->inverse)
+            hipLaunchKernelGGL((conv_halo_kernel<5, 2, GdnEpi>), grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y, gc->e);
+        else
+            hipLaunchKernelGGL((conv_halo_kernel<5, 1, GdnEpi>), grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y, gc->e);
+        return;
+    }
     if (L.halo == 5)
         hipLaunchKernelGGL(conv_halo_kernel<5>, grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y);
     else
         hipLaunchKernelGGL(conv_halo_kernel<3>, grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y);
-    if (a.ksplit > 1) {
-        const int VO = (a.y_vec && a.y_dtype == CAI_BF16) ? 8 : 4;
-        const int64_t total = (int64_t)L.mmax * ((a.Cout + VO - 1) / VO);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (total + 255) / 256));
-        hipLaunchKernelGGL((conv_splitk_reduce_kernel<bf16>), dim3(gx, 1), dim3(256), 0, st, a);
-    }
+    launch_splitk_reduce<bf16>(a, L, gc, st);
 }
 
 // the four-phase kernel (conv_quad.hip) where every block of it gets a CU: >= 256 tiles, no split
 static bool quad_grid(const ConvLaunch& L) { return L.halo_ph && L.hbn == 128 && L.ksplit == 1 && L.mtiles >= 256; }
 
-static void launch_conv_halo_phase(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
+static void launch_conv_halo_phase(const ConvArgs& a, const ConvLaunch& L, hipStream_t st,
+                                   const GdnCall* gc = nullptr) {
     const dim3 grid(L.halo_ph ? 4 * L.mtiles : L.mtiles, L.ntiles, a.ksplit);
+    if (gc && a.ksplit == 1) {    // GDN_HOST_PHASE
+        if (gc->inverse)
+            hipLaunchKernelGGL(conv_halo_phase_gdn_kernel<true>, grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y, gc->e);
+        else
+            hipLaunchKernelGGL(conv_halo_phase_gdn_kernel<false>, grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y, gc->e);
+        return;
+    }
     if (L.halo_ph) {
         if (quad_grid(L) && conv_quad_ok(a))
             launch_conv_halo_quad(a, L.tiles_x, L.tiles_y, L.mtiles, st);
@@ -3935,12 +4215,7 @@ static void launch_conv_halo_phase(const ConvArgs& a, const ConvLaunch& L, hipSt
                 hipLaunchKernelGGL((conv_halo_s1_kernel<128, false>), grid, dim3(512), 0, st, a, L.tiles_x, L.tiles_y);
         }
     }
-    if (a.ksplit > 1) {
-        const int VO = (a.y_vec && a.y_dtype == CAI_BF16) ? 8 : 4;
-        const int64_t total = (int64_t)L.mmax * ((a.Cout + VO - 1) / VO);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (total + 255) / 256));
-        hipLaunchKernelGGL((conv_splitk_reduce_kernel<bf16>), dim3(gx, a.nphase), dim3(256), 0, st, a);
-    }
+    launch_splitk_reduce<bf16>(a, L, gc, st);
 }
 
 static void launch_conv_small(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
@@ -3953,37 +4228,53 @@ static void launch_conv_small(const ConvArgs& a, const ConvLaunch& L, hipStream_
         hipLaunchKernelGGL((conv_small_kernel<2, 4>), grid, dim3(512), 0, st, a);
 }
 
+// gc: a forward GDN run by the host gdn_host names (bf16 only; the caller has checked that there is one)
 template <typename T>
-static void dispatch_conv(const ConvArgs& a, const ConvLaunch& L, hipStream_t st) {
+static void dispatch_conv(const ConvArgs& a, const ConvLaunch& L, hipStream_t st, const GdnCall* gc = nullptr) {
     if constexpr (sizeof(T) == 2) {
         if (L.small) {
             launch_conv_small(a, L, st);
             return;
         }
         if (L.halo) {
-            launch_conv_halo(a, L, st);
+            launch_conv_halo(a, L, st, gc);
             return;
         }
         if (L.halo_ph || L.halo_s1) {
-            launch_conv_halo_phase(a, L, st);
+            launch_conv_halo_phase(a, L, st, gc);
             return;
         }
         switch (L.cfg) {
-            case CFG_G1: launch_conv_glds<CfgG1>(a, L, st); return;
-            case CFG_G2: launch_conv_glds<CfgG2>(a, L, st); return;
-            case CFG_G3: launch_conv_glds<CfgG3>(a, L, st); return;
-            case CFG_G4: launch_conv_glds<CfgG4>(a, L, st); return;
-            case CFG_G5: launch_conv_glds<CfgG5>(a, L, st); return;
-            case CFG_G6: launch_conv_glds<CfgG6>(a, L, st); return;
+            case CFG_G1: launch_conv_glds<CfgG1>(a, L, st, gc); return;
+            case CFG_G2: launch_conv_glds<CfgG2>(a, L, st, gc); return;
+            case CFG_G3: launch_conv_glds<CfgG3>(a, L, st, gc); return;
+            case CFG_G4: launch_conv_glds<CfgG4>(a, L, st, gc); return;
+            case CFG_G5: launch_conv_glds<CfgG5>(a, L, st, gc); return;
+            case CFG_G6: launch_conv_glds<CfgG6>(a, L, st, gc); return;
             default: break;
         }
     }
     switch (L.cfg) {
-        case CFG_S: launch_conv<T, CfgS>(a, L, st); break;
-        case CFG_M: launch_conv<T, CfgM>(a, L, st); break;
-        case CFG_W: launch_conv<T, CfgW>(a, L, st); break;
-        default: launch_conv<T, CfgL>(a, L, st); break;
+        case CFG_S: launch_conv<T, CfgS>(a, L, st, gc); break;
+        case CFG_M: launch_conv<T, CfgM>(a, L, st, gc); break;
+        case CFG_W: launch_conv<T, CfgW>(a, L, st, gc); break;
+        default: launch_conv<T, CfgL>(a, L, st, gc); break;
     }
+}
+
+// the four-phase kernel takes this call when its output takes the register-direct epilogue (bf16, no mask / residual)
+static bool quad_taken(const cai_conv_geom* g, int dtype, int direction, int in_abs, const ConvLaunch& L) {
+    if (!quad_grid(L) || dtype != CAI_BF16) return false;
+    const Plan P = make_plan(g, dtype, direction);
+    ConvArgs a{};
+    a.nphase = P.nphase; a.Cin_pad = P.Cin_pad; a.Cout = P.kout_c; a.Npad = P.Npad; a.ksplit = L.ksplit;
+    a.out_step = P.phase ? g->stride : 1; a.in_abs = in_abs; a.y_vec = 1; a.y_dtype = CAI_BF16;
+    a.x_ld = P.Cin_pad;
+    for (int ph = 0; ph < P.nphase; ++ph) {
+        a.ph[ph].ntaps = P.ntaps[ph]; a.ph[ph].ntx = P.ntx[ph]; a.ph[ph].dy0 = P.dy0[ph];
+        a.ph[ph].dx0 = P.dx0[ph]; a.ph[ph].oy0 = P.oy0[ph]; a.ph[ph].ox0 = P.ox0[ph];
+    }
+    return conv_quad_ok(a);
 }
 
 // (A split-K "fold" -- the last-arriving block of a tile sums the slabs, no reduce launch -- was measured and
@@ -3993,7 +4284,8 @@ static int run_conv(const cai_conv_geom* g, int dtype, int direction, const void
                     const void* w, const float* bias, int act, float act_param, void* y, int y_dtype, int64_t ysb,
                     int64_t ysc, int64_t ysy, int64_t ysx, const void* aux, int aux_ld, int mask_mode,
                     float mask_param, void* workspace, size_t ws_bytes, void* stream, const char* name,
-                    const void* res = nullptr, int res_ld = 0, const void* res2 = nullptr, int res2_ld = 0) {
+                    const void* res = nullptr, int res_ld = 0, const void* res2 = nullptr, int res2_ld = 0,
+                    const GdnCall* gc = nullptr) {
     int rc = check_geom(g);
     if (rc) return rc;
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "%s: bad dtype", name);
@@ -4055,9 +4347,20 @@ static int run_conv(const cai_conv_geom* g, int dtype, int direction, const void
         d.K = P.ntaps[ph] * P.Cin_pad;
         d.w_off = (int64_t)ph * P.Npad * P.Kp;
     }
+    if (gc) {
+        const int host = gdn_host(L, dtype, a.Cout, quad_grid(L) && conv_quad_ok(a));
+        CAI_CHECK_ARG(host != GDN_HOST_NONE && direction == 0 && a.y_vec && y_dtype == CAI_BF16 &&
+                          act == CAI_ACT_NONE && !mask_mode && !res,
+                      "%s: no kernel runs the GDN of this conv's output (check cai_conv_gdn_fused first; bf16, 128 "
+                      "output channels, pixel-major output, no activation)", name);
+        CAI_CHECK_ARG(gc->e.gamma && gc->e.beta && gc->e.y && gc->e.y_ld >= a.Cout && gc->e.y_ld % 8 == 0 &&
+                          (((uintptr_t)gc->e.gamma | (uintptr_t)gc->e.y | (uintptr_t)gc->e.beta) & 15) == 0,
+                      "%s: GDN operands: gamma_op, beta and y 16-byte aligned, y_ld >= %d and a multiple of 8", name,
+                      a.Cout);
+    }
     if (L.mmax == 0) return CAI_OK;
     if (dtype == CAI_BF16)
-        dispatch_conv<bf16>(a, L, as_stream(stream));
+        dispatch_conv<bf16>(a, L, as_stream(stream), gc);
     else
         dispatch_conv<float>(a, L, as_stream(stream));
     CAI_LAUNCH_CHECK(name);
@@ -4536,6 +4839,22 @@ int cai_conv_fwd_res(const cai_conv_geom* g, int dtype, const void* x, int32_t x
                     nullptr, 0, CAI_MASK_NONE, 0.f, workspace, ws_bytes, stream, "conv_fwd_res", res, res_ld);
 }
 
+int cai_conv_gdn_fwd(const cai_conv_geom* g, int dtype, const void* x, int32_t x_ld, int32_t in_abs,
+                     const void* packed_w, const float* bias, void* xo, int64_t xsb, int64_t xsc, int64_t xsy,
+                     int64_t xsx, const void* gamma_op, const float* beta, int32_t inverse, void* y, int32_t y_ld,
+                     void* workspace, size_t ws_bytes, void* stream) {
+    CAI_CHECK_ARG(dtype == CAI_BF16, "conv_gdn_fwd: bf16 only");
+    GdnCall gc{};
+    gc.e.gamma = reinterpret_cast<const bf16*>(gamma_op);
+    gc.e.beta = beta;
+    gc.e.y = reinterpret_cast<bf16*>(y);
+    gc.e.y_ld = y_ld;
+    gc.inverse = inverse != 0;
+    return run_conv(g, dtype, 0, x, x_ld, in_abs, packed_w, bias, CAI_ACT_NONE, 0.f, xo, CAI_BF16, xsb, xsc, xsy, xsx,
+                    nullptr, 0, CAI_MASK_NONE, 0.f, workspace, ws_bytes, stream, "conv_gdn_fwd", nullptr, 0, nullptr, 0,
+                    &gc);
+}
+
 int cai_conv_dgrad(const cai_conv_geom* g, int dtype, const void* dy, int32_t dy_ld, const void* packed_wt, void* dx,
                    int32_t dx_ld, int32_t mask_mode, float mask_param, const void* aux, int32_t aux_ld,
                    void* workspace, size_t ws_bytes, void* stream) {
@@ -4572,6 +4891,26 @@ int cai_conv_dgrad_res2(const cai_conv_geom* g, int dtype, const void* dy, int32
                     workspace, ws_bytes, stream, "conv_dgrad_res2", res, res_ld, res2, res2_ld);
 }
 
+// the host of cai_conv_gdn_fwd for this geometry with a packed pixel-major bf16 output (GDN_HOST_*)
+static int gdn_host_of(const cai_conv_geom* g, int dtype, int32_t in_abs) {
+    if (check_geom(g) || dtype != CAI_BF16) return GDN_HOST_NONE;
+    const ConvLaunch L = conv_launch(g, dtype, 0, in_abs);
+    if (L.mmax == 0) return GDN_HOST_NONE;
+    return gdn_host(L, dtype, make_plan(g, dtype, 0).kout_c, quad_taken(g, dtype, 0, in_abs, L));
+}
+
+int32_t cai_conv_gdn_fused(const cai_conv_geom* g, int dtype, int32_t in_abs) { return gdn_host_of(g, dtype, in_abs); }
+
+const char* cai_conv_gdn_kernel_name(const cai_conv_geom* g, int dtype, int32_t in_abs, int32_t inverse) {
+    switch (gdn_host_of(g, dtype, in_abs)) {
+        case GDN_HOST_HALO: return inverse ? "conv_halo_kernel<5,igdn>" : "conv_halo_kernel<5,gdn>";
+        case GDN_HOST_PHASE: return inverse ? "conv_halo_phase_gdn_kernel<igdn>" : "conv_halo_phase_gdn_kernel<gdn>";
+        case GDN_HOST_REDUCE:
+            return inverse ? "conv_splitk_reduce_gdn_kernel<igdn>" : "conv_splitk_reduce_gdn_kernel<gdn>";
+        default: return "";
+    }
+}
+
 const char* cai_conv_kernel_name(const cai_conv_geom* g, int dtype, int direction, int32_t in_abs) {
     if (check_geom(g) || (dtype != CAI_BF16 && dtype != CAI_F32) || direction < 0 || direction > 2) return "";
     if (direction == 2) {
@@ -4591,19 +4930,7 @@ const char* cai_conv_kernel_name(const cai_conv_geom* g, int dtype, int directio
     const ConvLaunch L = conv_launch(g, dtype, direction, in_abs);
     if (L.halo) return L.halo == 5 ? "conv_halo_kernel<5>" : "conv_halo_kernel<3>";
     if (L.halo_ph) {
-        if (quad_grid(L) && dtype == CAI_BF16) {
-            // the four-phase kernel when the output takes the register-direct epilogue (bf16, no mask / residual)
-            const Plan P = make_plan(g, dtype, direction);
-            ConvArgs a{};
-            a.nphase = P.nphase; a.Cin_pad = P.Cin_pad; a.Cout = P.kout_c; a.Npad = P.Npad; a.ksplit = L.ksplit;
-            a.out_step = P.phase ? g->stride : 1; a.in_abs = in_abs; a.y_vec = 1; a.y_dtype = CAI_BF16;
-            a.x_ld = P.Cin_pad;
-            for (int ph = 0; ph < P.nphase; ++ph) {
-                a.ph[ph].ntaps = P.ntaps[ph]; a.ph[ph].ntx = P.ntx[ph]; a.ph[ph].dy0 = P.dy0[ph];
-                a.ph[ph].dx0 = P.dx0[ph]; a.ph[ph].oy0 = P.oy0[ph]; a.ph[ph].ox0 = P.ox0[ph];
-            }
-            if (conv_quad_ok(a)) return "conv_halo_quad_kernel";
-        }
+        if (quad_taken(g, dtype, direction, in_abs, L)) return "conv_halo_quad_kernel";
         return L.hbn == 192 ? "conv_halo_phase_kernel<192>" : "conv_halo_phase_kernel";
     }
     if (L.halo_s1)

@@ -44,7 +44,16 @@ struct ConvArgs {
     PhaseDesc ph[4];
 };
 
-// The four-phase k5 s2 kernel (conv_quad.hip).  conv_quad_ok: the phase descriptors and the output take its
+// A forward GDN / IGDN run in the epilogue of the conv that produces its input (cai_conv_gdn_fwd): the conv's
+// output x goes to ConvArgs::y as always, y = GDN(x) to `y` here (pixel-major bf16, row stride y_ld).
+struct GdnEpi {
+    const bf16* gamma;   // gamma_op of cai_gdn_reparam: [C][C] bf16 row-major
+    const float* beta;   // [C]
+    bf16* y;
+    int y_ld;
+};
+
+// The four-phase k5 s2 kernel (conv_quad.hip). conv_quad_ok: the phase descriptors and the output take its
 // path (128 input channels, <= 128 output channels, k5 s2 p2 phases, bf16 output by the register-direct
 // epilogue without mask or residual); the caller has checked the grid (>= 256 tiles, no split).
 bool conv_quad_ok(const ConvArgs& a);

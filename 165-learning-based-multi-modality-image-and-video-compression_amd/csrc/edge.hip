@@ -23,7 +23,9 @@
 // layout of dW / db.
 #include "common.hpp"
 #include "reduce_jobs.hpp"
+#include "conv_args.hpp"
 #include "edge_frag.hpp"
+#include "gdn_tile.hpp"
 #include "mfma.hpp"
 
 #include <algorithm>
@@ -56,6 +58,7 @@ struct EdgeArgs {
     bf16* sbf;            // packed superpixels [B][Hs][Ws][16] bf16 (wgrad DMA path)
     float* cs_part;       // per-pack-block fp32 column sums of the image side [npack][16]
     int npack, ipb;       // pack blocks, superpixels per pack block
+    GdnEpi gdn;           // edge_s2d_kernel<.., GDN = true>: the forward GDN of the output (cai_edge_conv_gdn_fwd)
 };
 
 // s2d A/B knobs, measured on MI355X (the C2 g_a[0] forward / g_s[6] input gradient, 16 x 128 x 128 x 128
@@ -279,10 +282,23 @@ __device__ __forceinline__ void s_store_b(const SPreB<C>& L, char* Ss) {
     *reinterpret_cast<u32x4*>(Ss + dyi * SROW + j * 32 + 16) = __builtin_bit_cast(u32x4, hi);
 }
 
-template <int C, int NPW, int PD>
-__global__ __launch_bounds__(NT) void edge_s2d_kernel(const EdgeArgs A) {
+// GDN (N = 128, the conv forward; cai_edge_conv_gdn_fwd): the forward GDN of the output in the same pass.  Wave w's
+// bf16 chunk "channels 32 w + 8 g_ .. +8 of pixel 16 m + i16" of its four 16-pixel tiles is K block w of the
+// GDN's B operand, already lane-local: per tile the waves exchange the squared chunks through an LDS image
+// (64 px x 128 ch, rows padded by 16 bytes; one more barrier per tile, the image is free again at the next tile's
+// staging barrier), wave w runs output blocks 2 w, 2 w + 1 over the four K blocks (32 MFMAs, its 8 gamma
+// fragments in registers) with the step of gdn_tile.hpp, and y leaves as the same 16-byte chunks as x.
+// It is an instantiation of its own (GDN = true, the GdnEpi in A.gdn): the others keep their instructions.
+template <int C, int NPW, int PD, bool GDN = false>
+__global__ __launch_bounds__(NT, GDN ? 3 : 0) void edge_s2d_kernel(const EdgeArgs A) {   // GDN: three waves per SIMD
     constexpr int N = 64 * NPW, NTL = N / 16;
+    static_assert(!GDN || NPW == 2, "the GDN variant: 128 output channels");
+    constexpr int QRS = 2 * 128 + 16;
     __shared__ __attribute__((aligned(16))) char Ss[2][3 * SROW];
+    __shared__ __attribute__((aligned(16))) char Lq[GDN ? TB * QRS : 16];
+    __shared__ __attribute__((aligned(16))) float Lb[GDN ? 128 : 4];
+    // each lane's own x chunks wait here for the barrier, not in registers (three waves per SIMD: 168 registers)
+    __shared__ __attribute__((aligned(16))) char Lx[GDN ? NT * 4 * 16 : 16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g_ = lane >> 4, i16 = lane & 15;
     const int tiles = A.B * A.Hs * A.ncb;
@@ -300,6 +316,19 @@ __global__ __launch_bounds__(NT) void edge_s2d_kernel(const EdgeArgs A) {
         const_cast<float*>(A.img), (short)0, A.B * A.C * 16 * A.Hs * A.Ws, 0x00020000);
     const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(
         A.out_feat, (short)0, A.B * A.Hs * A.Ws * A.out_ld * 2, 0x00020000);
+    __amdgpu_buffer_rsrc_t yrr = orr;
+    u32x4 ga[2][4];
+    const GdnEpi* const ge = &A.gdn;
+    if constexpr (GDN) {
+        yrr = __builtin_amdgcn_make_buffer_rsrc(ge->y, (short)0, A.B * A.Hs * A.Ws * ge->y_ld * 2, 0x00020000);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const bf16* row = ge->gamma + perm_ch(2 * wave + h, i16) * 128 + 8 * g_;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) ga[h][kb] = *reinterpret_cast<const u32x4*>(row + 32 * kb);
+        }
+        if (threadIdx.x < 128) Lb[threadIdx.x] = ge->beta[threadIdx.x];   // read after the first tile's barriers
+    }
     auto decode = [&](int t, int& n, int& a, int& b0) {
         if (t >= t1) t -= TS;   // past the run: reload the last tile (harmless, keeps the load count fixed)
         a = t % A.Hs;
@@ -368,6 +397,40 @@ __global__ __launch_bounds__(NT) void edge_s2d_kernel(const EdgeArgs A) {
             }
         }
         const int rowoff = ((tn * A.Hs + ta) * A.Ws + tb0) * A.out_ld;
+        if constexpr (GDN) {
+            char* const lx = Lx + threadIdx.x * 64;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int px = 16 * m + i16;
+                const bool ok = tb0 + px < A.Ws;
+                bf16x8 h;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    h[r] = (bf16)acc[m][0][r];
+                    h[4 + r] = (bf16)acc[m][1][r];
+                }
+                const u32x4 xc = __builtin_bit_cast(u32x4, h);
+                *reinterpret_cast<u32x4*>(Lq + px * QRS + (32 * wave + 8 * g_) * 2) = sq_chunk<bf16>(xc);
+                *reinterpret_cast<u32x4*>(lx + 16 * m) = xc;
+                const unsigned off = (unsigned)((rowoff + px * A.out_ld + wave * 32 + 8 * g_) * 2);
+                __builtin_amdgcn_raw_buffer_store_b128(xc, orr, ok ? off : EOOB, 0, CAI_EDGE_ST_AUX);
+            }
+            __syncthreads();
+            const int yoff = ((tn * A.Hs + ta) * A.Ws + tb0) * ge->y_ld;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int px = 16 * m + i16;
+                const bool ok = tb0 + px < A.Ws;
+                u32x4 q[4], xs[1] = {*reinterpret_cast<const u32x4*>(lx + 16 * m)}, yv[1];
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb)
+                    q[kb] = *reinterpret_cast<const u32x4*>(Lq + px * QRS + (32 * kb + 8 * g_) * 2);
+                gdn_tile_fwd_part<128, false, true, 1>(ga, Lb, xs, q, yv, g_, wave);
+                const unsigned off = (unsigned)((yoff + px * ge->y_ld + wave * 32 + 8 * g_) * 2);
+                __builtin_amdgcn_raw_buffer_store_b128(yv[0], yrr, ok ? off : EOOB, 0, CAI_EDGE_ST_AUX);
+            }
+            return;
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int px = 16 * m + i16;
@@ -987,7 +1050,8 @@ template <int C>
 void launch_s2d(const EdgeArgs& A, hipStream_t st) {
     const int bpc = s2d_blocks_per_cu();
     // the kernel addresses image and output with 32-bit byte offsets: batches of < 2 GiB each
-    const int64_t per_img = std::max<int64_t>((int64_t)A.C * 16 * A.Hs * A.Ws, (int64_t)A.Hs * A.Ws * A.out_ld * 2);
+    const int64_t per_img = std::max<int64_t>((int64_t)A.C * 16 * A.Hs * A.Ws,
+                                              (int64_t)A.Hs * A.Ws * std::max(A.out_ld, A.gdn.y ? A.gdn.y_ld : 0) * 2);
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(A.B, ((int64_t)1 << 31) / 2 / per_img));
     for (int b = 0; b < A.B; b += nb) {
         EdgeArgs P = A;
@@ -996,6 +1060,11 @@ void launch_s2d(const EdgeArgs& A, hipStream_t st) {
         P.out_feat = A.out_feat + (int64_t)b * A.Hs * A.Ws * A.out_ld;
         const int pt = P.B * P.Hs * P.ncb;
         const int grid = bpc == 0 ? pt : std::min(pt, 256 * bpc);
+        if (A.gdn.y) {    // N == 128, the caller has checked
+            P.gdn.y = A.gdn.y + (int64_t)b * A.Hs * A.Ws * A.gdn.y_ld;
+            edge_s2d_kernel<C, 2, CAI_EDGE_S2D_PD, true><<<grid, NT, 0, st>>>(P);
+            continue;
+        }
         if (CAI_EDGE_S2D_PD == 2) {
             if (A.N == 128)
                 edge_s2d_kernel<C, 2, 2><<<grid, NT, 0, st>>>(P);
@@ -1133,6 +1202,33 @@ int cai_edge_conv_fwd(const cai_conv_geom* g, const float* x, const void* frag, 
     A.out_ld = y_ld;
     EDGE_BY_C(launch_s2d, A, as_stream(stream));
     CAI_LAUNCH_CHECK("edge_conv_fwd");
+    return CAI_OK;
+}
+
+int32_t cai_edge_conv_gdn_fused(const cai_conv_geom* g) {
+    EdgeArgs A;
+    return g && !g->transposed && edge_geo(g, CAI_BF16, A) && A.N == 128;
+}
+
+int cai_edge_conv_gdn_fwd(const cai_conv_geom* g, const float* x, const void* frag, const float* bias, void* xo,
+                          int32_t xo_ld, const void* gamma_op, const float* beta, void* y, int32_t y_ld,
+                          void* stream) {
+    EdgeArgs A;
+    CAI_CHECK_ARG(cai_edge_conv_gdn_fused(g) && edge_geo(g, CAI_BF16, A),
+                  "edge_conv_gdn_fwd: no GDN variant for this geometry (check cai_edge_conv_gdn_fused first)");
+    CAI_CHECK_ARG(x && frag && xo && y && gamma_op && beta && aligned16(xo) && aligned16(y) && aligned16(frag) &&
+                      aligned16(gamma_op) && ((uintptr_t)x & 7) == 0,
+                  "edge_conv_gdn_fwd: null or misaligned pointer");
+    CAI_CHECK_ARG(xo_ld >= A.N && xo_ld % 8 == 0 && y_ld >= A.N && y_ld % 8 == 0, "edge_conv_gdn_fwd: ld %d / %d",
+                  xo_ld, y_ld);
+    A.img = x;
+    A.frag = static_cast<const u32x4*>(frag);
+    A.bias = bias;
+    A.out_feat = static_cast<bf16*>(xo);
+    A.out_ld = xo_ld;
+    A.gdn = GdnEpi{static_cast<const bf16*>(gamma_op), beta, static_cast<bf16*>(y), y_ld};
+    EDGE_BY_C(launch_s2d, A, as_stream(stream));
+    CAI_LAUNCH_CHECK("edge_conv_gdn_fwd");
     return CAI_OK;
 }
 

@@ -22,6 +22,7 @@
 // [block][C*C + C] slab as the fused kernel's, reduced by the GDN reduce job (reduce_jobs.hip).
 // Pixels past npix load as 0 (buffer loads out of range): x = dy = 0 gives u = 0, so they add nothing.
 #include "common.hpp"
+#include "gdn_tile.hpp"
 #include "mfma.hpp"
 
 #include <stdlib.h>
@@ -37,8 +38,6 @@ namespace {
 #endif
 
 constexpr unsigned LANE_OOB = 0x80000000u;   // beyond every buffer: loads return 0, stores are dropped
-
-__device__ __forceinline__ int perm_ch(int cb, int m) { return 32 * (cb >> 1) + 8 * (m >> 2) + 4 * (cb & 1) + (m & 3); }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int64_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
@@ -72,29 +71,6 @@ __device__ __forceinline__ void afrag_load(u32x4 (&a)[C / 16][C / 32], const bf1
         const bf16* row = mat + (int64_t)perm_ch(cb, p) * C + 8 * g;
 #pragma unroll
         for (int kb = 0; kb < C / 32; ++kb) a[cb][kb] = *reinterpret_cast<const u32x4*>(row + 32 * kb);
-    }
-}
-
-// The workgroup's copy of NM consecutive [C][C] bf16 matrices in LDS (rows padded by 16 bytes: the fragment reads
-// of 16 rows at one column spread over the banks): one coalesced global read per workgroup instead of one
-// fragment gather per wave.  Ends with a barrier.
-template <int C, int NM, int NT>
-__device__ __forceinline__ void stage_mats(char* lds, const bf16* mat) {
-    constexpr int RSG = 2 * C + 16, CH = 2 * C / 16;   // row stride (bytes), 16-byte chunks per row
-    for (int i = threadIdx.x; i < NM * C * CH; i += NT) {
-        const int row = i / CH, ch = i - (i / CH) * CH;
-        *reinterpret_cast<u32x4*>(lds + row * RSG + ch * 16) = *reinterpret_cast<const u32x4*>(mat + (int64_t)row * C + ch * 8);
-    }
-    __syncthreads();
-}
-template <int C>
-__device__ __forceinline__ void afrag_lds(u32x4 (&a)[C / 16][C / 32], const char* img, int p, int g) {
-    constexpr int RSG = 2 * C + 16;
-#pragma unroll
-    for (int cb = 0; cb < C / 16; ++cb) {
-        const char* row = img + perm_ch(cb, p) * RSG + 16 * g;
-#pragma unroll
-        for (int kb = 0; kb < C / 32; ++kb) a[cb][kb] = *reinterpret_cast<const u32x4*>(row + 64 * kb);
     }
 }
 
@@ -137,26 +113,7 @@ __global__ __launch_bounds__(256, OCC) void gdn_fwd_lane_kernel(const bf16* __re
         }
         chunk_load<KB>(rx, xr, nxt * 16 + p, npix, x_ld, g);
         u32x4 yv[KB];
-#pragma unroll
-        for (int kx = 0; kx < KB; ++kx) {
-            const bf16x8 xv = __builtin_bit_cast(bf16x8, xc[kx]);
-            bf16x8 yy;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb) acc = mma16<bf16>(ga[2 * kx + h][kb], q[kb], acc);
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(Lb + 32 * kx + 8 * g + 4 * h);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float nv = acc[r] + bq[r];
-                    const float rs = rsqrtf(nv);
-                    yy[4 * h + r] = (bf16)((float)xv[4 * h + r] * (INV ? nv * rs : rs));
-                }
-            }
-            yv[kx] = __builtin_bit_cast(u32x4, yy);
-            if constexpr (OCC == 2) __builtin_amdgcn_sched_barrier(0);   // bound the live accumulators
-        }
+        gdn_tile_fwd<C, INV, OCC == 2>(ga, Lb, xc, q, yv, g);
         chunk_store<KB>(yv, yr, cur * 16 + p, npix, y_ld, g);
     };
     if constexpr (NSET == 2) {

@@ -149,6 +149,31 @@ int cai_conv_fwd_res(const cai_conv_geom* g, int dtype,
                      void* y, int y_dtype, int64_t ysb, int64_t ysc, int64_t ysy, int64_t ysx,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* forward with the GDN / IGDN that consumes the output in the same call
+ * (layers/gdn.py:77-92 after a conv() / deconv() of models/utils.py):
+ *   xo = conv(x) + bias          at xo[b*xsb + c*xsc + oy*xsy + ox*xsx], bf16
+ *   y  = GDN(xo)  (inverse != 0: IGDN), pixel-major bf16 with ld y_ld
+ * with gamma_op / beta as cai_gdn_reparam writes them.  Both outputs are
+ * bit-identical to cai_conv_fwd followed by cai_gdn_fwd; the read of xo by a
+ * separate GDN launch, and that launch, are saved.  bf16 only, 128 output
+ * channels, xo pixel-major (xsc == 1), no activation; the kernels that can
+ * host the GDN are conv_halo_kernel<5>, conv_halo_phase_kernel<128> (both
+ * without split-K) and the split-K reduce of any split call.
+ * cai_conv_gdn_fused: nonzero when a call of this geometry (with a packed
+ * pixel-major output) takes the fused form -- otherwise cai_conv_gdn_fwd
+ * fails with CAI_EINVAL and the caller runs the two calls.
+ * cai_conv_gdn_kernel_name: the kernel that runs the GDN then ("" when not
+ * fused); the conv kernel of a split call stays cai_conv_kernel_name's. */
+int cai_conv_gdn_fwd(const cai_conv_geom* g, int dtype,
+                     const void* x, int32_t x_ld, int32_t in_abs,
+                     const void* packed_w, const float* bias,
+                     void* xo, int64_t xsb, int64_t xsc, int64_t xsy, int64_t xsx,
+                     const void* gamma_op, const float* beta, int32_t inverse,
+                     void* y, int32_t y_ld,
+                     void* workspace, size_t ws_bytes, void* stream);
+int32_t cai_conv_gdn_fused(const cai_conv_geom* g, int dtype, int32_t in_abs);
+const char* cai_conv_gdn_kernel_name(const cai_conv_geom* g, int dtype, int32_t in_abs, int32_t inverse);
+
 /* input gradient: dx = mask(aux) * conv_input_grad(dy).  dy pixel-major
  * (ld dy_ld), dx pixel-major (ld dx_ld), aux pixel-major (ld aux_ld) or NULL. */
 int cai_conv_dgrad(const cai_conv_geom* g, int dtype,
@@ -354,6 +379,16 @@ int cai_edge_pack_describe(const cai_conv_geom* g, int dtype, int direction, con
 /* Conv forward: y = conv(x) + bias, x NCHW fp32, y pixel-major bf16. */
 int cai_edge_conv_fwd(const cai_conv_geom* g, const float* x, const void* frag, const float* bias, void* y,
                       int32_t y_ld, void* stream);
+/* cai_edge_conv_fwd with the forward GDN that consumes its output in the same
+ * launch (the GDN variant of edge_s2d_kernel, 128 output channels): xo = the
+ * conv's output (ld xo_ld), y = GDN(xo) (ld y_ld), gamma_op / beta as
+ * cai_gdn_reparam writes them; both bit-identical to cai_edge_conv_fwd followed
+ * by cai_gdn_fwd.  cai_edge_conv_gdn_fused: nonzero when the geometry has the
+ * variant (otherwise the call fails with CAI_EINVAL). */
+int cai_edge_conv_gdn_fwd(const cai_conv_geom* g, const float* x, const void* frag, const float* bias, void* xo,
+                          int32_t xo_ld, const void* gamma_op, const float* beta, void* y, int32_t y_ld,
+                          void* stream);
+int32_t cai_edge_conv_gdn_fused(const cai_conv_geom* g);
 /* ConvTranspose forward: y (NCHW fp32) = deconv(x) + bias, x pixel-major bf16. */
 int cai_edge_deconv_fwd(const cai_conv_geom* g, const void* x, int32_t x_ld, const void* frag, const float* bias,
                         float* y, void* stream);
