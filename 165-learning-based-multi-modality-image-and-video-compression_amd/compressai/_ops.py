@@ -1926,9 +1926,11 @@ class RdLossFnUnfused(torch.autograd.Function):
         lib.cai_sqdiff_bwd(_p(xh), _p(tg), n, _p(gmt), 2.0 / n, _p(dxh), st)
         dliks = []
         for lr, (ld, lp, C), shp in zip(lrs, meta, lshapes):
-            d, dbuf = empty_rows_like(shp, torch.float32, xh.device)
+            # cai_log_bwd writes g[p * ld + c], the likelihood's own row pitch: the gradient buffer has that
+            # pitch too (a dense [pixels][C] buffer is lp * (ld - C) floats too short when ld > C)
+            dbuf = torch.empty((shp[0], *shp[2:], ld), dtype=torch.float32, device=xh.device)
             lib.cai_log_bwd(_p(lr), lp, C, ld, _p(gbt), bpp_coef, _p(dbuf), st)
-            dliks.append(d)
+            dliks.append(dbuf[..., :C].movedim(-1, 1))
         return (dxh.view(xshape), None, None, None, *dliks)
 
 
