@@ -232,6 +232,14 @@ SIGNATURES = {
     "cai_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _F, c_int32, _P, c_size_t, _P]),
     "cai_act_bwd": (_I, [_I, _F, _P, c_int32, _P, c_int32, _P, c_int32, _I64, c_int32, _I, _P]),
     "cai_cast": (_I, [_P, _I, _P, _I, _I64, _P]),
+    "cai_qrelu_fwd": (_I, [_I, _P, c_int32, _P, c_int32, _I64, c_int32, c_int32, _P]),
+    "cai_qrelu_bwd": (_I, [_I, _P, c_int32, _P, c_int32, _P, c_int32, _I64, c_int32, c_int32, _F, _P]),
+    "cai_ssf_workspace_bytes": (_S, [c_int32, c_int32, c_int32, c_int32]),
+    "cai_ssf_volume_fwd": (_I, [_P, c_int32, c_int32, c_int32, _F, c_int32, _P, _P, _S, _P]),
+    "cai_ssf_volume_bwd": (_I, [_P, c_int32, c_int32, c_int32, _F, c_int32, _P, _P, _S, _P]),
+    "cai_ssf_warp_fwd": (_I, [_P, _P, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "cai_ssf_warp_bwd": (_I, [_P, _P, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                              _P]),
 }
 
 

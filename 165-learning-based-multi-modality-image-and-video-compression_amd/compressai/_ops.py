@@ -2615,3 +2615,142 @@ class ChannelAffineFn(torch.autograd.Function):
         lib.cai_channel_mean(dcode(dt), _p(gp), gld, _p(xp), xld, B, H * W, C, _p(dgamma), 1.0, _p(ws), nb, _stream())
         lib.cai_channel_mean(dcode(dt), _p(gp), gld, None, 0, B, H * W, C, _p(dbeta), 1.0, _p(ws), nb, _stream())
         return dx, dgamma, dbeta
+
+
+# ---------------------------------------------------------------------------
+# ScaleSpaceFlow (models/video/google.py): QReLU, the Gaussian scale-space volume and its trilinear warp --
+# csrc/elementwise.hip, csrc/ssf.hip
+# ---------------------------------------------------------------------------
+
+class QReluFn(torch.autograd.Function):
+    """QReLU (layers/layers.py): clamp(x, 0, 2^bit_depth - 1); backward g inside the range,
+    g exp(-alpha^beta |2 x / max - 1|^beta) outside.  Pixel-major in, pixel-major out, in the compute dtype."""
+
+    @staticmethod
+    def forward(ctx, x, bit_depth: int, beta: float):
+        _check_cuda(x)
+        if x.dim() != 4:
+            raise ValueError(f"QReLU expects a [B, C, H, W] tensor, got {tuple(x.shape)}")
+        dt = compute_dtype()
+        xp, xld = to_pm(x, dt, _vec(dt))
+        y, yld = _out_pm_like(x, dt)
+        B, C, H, W = x.shape
+        _ledger.run(lambda: lib.cai_qrelu_fwd(dcode(dt), _p(xp), xld, _p(y), yld, B * H * W, C, int(bit_depth),
+                                              _stream()),
+                    "qrelu_fwd", "qrelu_kernel", 0, 2 * B * H * W * C * _es(dt), dt)
+        ctx.cfg = (int(bit_depth), float(beta), dt, xld)
+        ctx.save_for_backward(xp)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (xp,) = ctx.saved_tensors
+        bits, beta, dt, xld = ctx.cfg
+        B, C, H, W = xp.shape
+        gp, gld = to_pm(g, dt, _vec(dt))
+        dx, dld = _out_pm_like(xp, dt)
+        _ledger.run(lambda: lib.cai_qrelu_bwd(dcode(dt), _p(xp), xld, _p(gp), gld, _p(dx), dld, B * H * W, C, bits, beta,
+                                              _stream()),
+                    "qrelu_bwd", "qrelu_kernel", 0, 3 * B * H * W * C * _es(dt), dt)
+        return dx, None, None
+
+
+def _ssf_ws(planes, H, W, levels, device):
+    nb = lib.cai_ssf_workspace_bytes(planes, H, W, levels)
+    if nb == 0:
+        raise ValueError(f"cai_ssf_workspace_bytes: {lib.cai_last_error().decode(errors='replace')}")
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+class ScaleSpaceVolumeFn(torch.autograd.Function):
+    """gaussian_volume(x, sigma, num_levels): [N, C, H, W] -> fp32 [N, C, num_levels + 1, H, W] (csrc/ssf.hip).
+    Forward 2 + sum_{l >= 2} l launches, backward the exact adjoints in gather form (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, sigma: float, num_levels: int):
+        _check_cuda(x)
+        if x.dim() != 4:
+            raise ValueError(f"gaussian_volume expects a [N, C, H, W] tensor, got {tuple(x.shape)}")
+        N, C, H, W = x.shape
+        levels = int(num_levels)
+        xf = x.float().contiguous()
+        ws, nb = _ssf_ws(N * C, H, W, levels, x.device)
+        vol = torch.empty((N, C, levels + 1, H, W), dtype=torch.float32, device=x.device)
+        _ledger.run(lambda: lib.cai_ssf_volume_fwd(_p(xf), N * C, H, W, float(sigma), levels, _p(vol), _p(ws), nb,
+                                                   _stream()),
+                    "ssf_volume_fwd", "ssf_blur_kernel", 0, 4 * xf.numel() * (levels + 2), torch.float32)
+        ctx.cfg = (float(sigma), levels, tuple(x.shape), x.dtype)
+        return vol
+
+    @staticmethod
+    def backward(ctx, g):
+        sigma, levels, shape, dtype = ctx.cfg
+        N, C, H, W = shape
+        gf = g.float().contiguous()
+        ws, nb = _ssf_ws(N * C, H, W, levels, g.device)
+        dx = torch.empty(shape, dtype=torch.float32, device=g.device)
+        _ledger.run(lambda: lib.cai_ssf_volume_bwd(_p(gf), N * C, H, W, sigma, levels, _p(dx), _p(ws), nb, _stream()),
+                    "ssf_volume_bwd", "ssf_blurt_kernel", 0, 4 * dx.numel() * (levels + 2), torch.float32)
+        return dx.to(dtype), None, None
+
+
+class ScaleSpaceWarpFn(torch.autograd.Function):
+    """warp_volume(volume, flow, scale_field) with motion_info = (flow_x, flow_y, scale) [N, 3, H, W] read in
+    place through its strides: x_pred [N, C, H, W] and, with x_cur, x_res = x_cur - x_pred from the same launch.
+    Backward: d_motion_info in one launch; d_volume (fp32 atomic adds into a zeroed buffer, so its low bits
+    depend on the order of the adds) only when the volume requires grad."""
+
+    @staticmethod
+    def forward(ctx, volume, motion_info, x_cur=None):
+        _check_cuda(volume, motion_info, x_cur)
+        if volume.dim() != 5:
+            raise ValueError(f"Invalid number of dimensions for volume {volume.dim()}")
+        N, C, D, H, W = volume.shape
+        if tuple(motion_info.shape) != (N, 3, H, W):
+            raise ValueError(f"motion_info must be [{N}, 3, {H}, {W}], got {tuple(motion_info.shape)}")
+        vol = volume.float().contiguous()
+        mi = motion_info if motion_info.dtype == torch.float32 else motion_info.float()
+        ms = (ctypes.c_int64 * 4)(*mi.stride())
+        x_pred = torch.empty((N, C, H, W), dtype=torch.float32, device=vol.device)
+        xc = xr = None
+        if x_cur is not None:
+            if tuple(x_cur.shape) != (N, C, H, W):
+                raise ValueError(f"x_cur must be [{N}, {C}, {H}, {W}], got {tuple(x_cur.shape)}")
+            xc = x_cur.float().contiguous()
+            xr = torch.empty_like(x_pred)
+        _ledger.run(lambda: lib.cai_ssf_warp_fwd(_p(vol), _p(mi), ms, N, C, D, H, W, _p(x_pred), _p(xc), _p(xr),
+                                                 _stream()),
+                    "ssf_warp_fwd", "ssf_warp_fwd_kernel", 0, 4 * (8 * x_pred.numel() + 3 * N * H * W), torch.float32)
+        ctx.save_for_backward(vol, mi)
+        ctx.cfg = (motion_info.dtype, x_cur is not None)
+        ctx.set_materialize_grads(False)
+        if x_cur is None:
+            return x_pred
+        return x_pred, xr
+
+    @staticmethod
+    def backward(ctx, g_pred, g_res=None):
+        vol, mi = ctx.saved_tensors
+        mdtype, has_cur = ctx.cfg
+        N, C, D, H, W = vol.shape
+        none = (None, None, None)
+        if g_pred is None and g_res is None:
+            return none
+        gp = None if g_pred is None else g_pred.float().contiguous()
+        gr = None if g_res is None else g_res.float().contiguous()
+        ms = (ctypes.c_int64 * 4)(*mi.stride())
+        dm = dv = None
+        if ctx.needs_input_grad[1]:
+            dm = torch.empty((N, 3, H, W), dtype=torch.float32, device=vol.device)
+        if ctx.needs_input_grad[0]:
+            dv = torch.zeros_like(vol)
+        if dm is not None or dv is not None:
+            _ledger.run(lambda: lib.cai_ssf_warp_bwd(_p(vol), _p(mi), ms, N, C, D, H, W, _p(gp), _p(gr), _p(dm), _p(dv),
+                                                     _stream()),
+                        "ssf_warp_bwd", "ssf_warp_bwd_kernel", 0,
+                        4 * ((9 if dm is not None else 0) + (9 if dv is not None else 0)) * N * C * H * W,
+                        torch.float32)
+        dcur = None
+        if has_cur and ctx.needs_input_grad[2]:
+            dcur = gr
+        return (dv, None if dm is None else dm.to(mdtype), dcur)

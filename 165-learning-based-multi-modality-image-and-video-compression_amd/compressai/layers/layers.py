@@ -21,13 +21,13 @@ import torch
 import torch.nn as nn
 
 from .._native import ACT_LEAKY, ACT_NONE, ACT_RELU, MASK_LEAKY, MASK_POS
-from .._ops import (AddActFn, AttentionBlockFn, GateFn, ResidualBlockFn, ResidualChainFn, _ab_side, fan_out,
+from .._ops import (AddActFn, AttentionBlockFn, GateFn, QReluFn, ResidualBlockFn, ResidualChainFn, _ab_side, fan_out,
                     residual_fusable)
 from .conv import Conv2d, ConvTranspose2d, PixelShuffle, Sequential
 from .gdn import GDN
 
 __all__ = ["MaskedConv2d", "conv1x1", "conv3x3", "subpel_conv3x3", "PixelShuffle", "ResidualBlockWithStride",
-           "ResidualBlockUpsample", "ResidualBlock", "AttentionBlock"]
+           "ResidualBlockUpsample", "ResidualBlock", "AttentionBlock", "QReLU"]
 
 _SLOPE = 0.01   # nn.LeakyReLU() default negative_slope
 
@@ -220,3 +220,10 @@ class AttentionBlock(nn.Module):
         sb, pb = _chain_specs(ub)
         c3 = self.conv_b[3]
         return AttentionBlockFn.apply(x, sa, sb, c3._spec(in_mask=MASK_POS), *pa, *pb, c3.weight, c3.bias)
+
+
+class QReLU(QReluFn):
+    """QReLU (layers.py:247-296; Balle, Johnston, Minnen, "Integer networks for data compression with
+    latent-variable models", ICLR 2019): ``QReLU.apply(input, bit_depth, beta)`` clamps to [0, 2^bit_depth - 1]; the
+    backward passes the gradient inside the range and scales it by exp(-alpha^beta |2 x / max - 1|^beta)
+    outside (alpha = 0.9943258522851727).  One HIP launch each way (csrc/elementwise.hip)."""

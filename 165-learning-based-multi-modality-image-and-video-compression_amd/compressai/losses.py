@@ -45,3 +45,26 @@ class RateDistortionLoss(nn.Module):
         ms, _ = MsSsimFn.apply(output["x_hat"], target, 1.0)
         loss = lmbda * (1.0 - ms) + bpp
         return {"bpp_loss": bpp, "ms_ssim_loss": ms, "loss": loss}
+
+
+class VideoRateDistortionLoss(nn.Module):
+    """Rate-distortion loss of a ScaleSpaceFlow forward: per frame lmbda * 255^2 * mse + bpp through the RD
+    kernels (2 likelihood tensors for the keyframe, 4 for an inter frame), averaged over the frames."""
+
+    def __init__(self, lmbda=1e-2):
+        super().__init__()
+        self.lmbda = float(lmbda)
+
+    def forward(self, output, target):
+        if not isinstance(target, (list, tuple)) or len(target) != len(output["x_hat"]):
+            raise ValueError("VideoRateDistortionLoss: target must be the list of frames the model was given")
+        fn = RdLossFnUnfused if _ops._RD_UNFUSED else RdLossFn
+        n = len(target)
+        tot = {"loss": None, "mse_loss": None, "bpp_loss": None}
+        for x_hat, x, frame_liks in zip(output["x_hat"], target, output["likelihoods"]):
+            N, _, H, W = x.size()
+            liks = [lk for stream in frame_liks.values() for lk in stream.values()]
+            loss, mse, bpp = fn.apply(x_hat, x, self.lmbda * 255.0 ** 2, N * H * W, *liks)
+            for k, v in (("loss", loss), ("mse_loss", mse), ("bpp_loss", bpp)):
+                tot[k] = v if tot[k] is None else tot[k] + v
+        return {k: v / n for k, v in tot.items()}

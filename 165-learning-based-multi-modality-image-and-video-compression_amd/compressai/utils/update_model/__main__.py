@@ -10,8 +10,10 @@ ARCH: a zoo name (``bmshj2018-hyperprior``, ``cheng2020-attn``, ...), one of the
 (``factorized-prior``, ``scale-hyperprior``, ``mean-scale-hyperprior``, ``jarhp``) or ``Guided_compresser`` /
 ``Master_compresser`` (the paired codec, width 512 x height 640 as the reference builds it).  Differences from
 the reference: checkpoints are read with ``torch.load(weights_only=True)`` (tensors only, nothing executed);
-the video model (``ssf2020``) and the depth-map variants (``cheng2020-attn_R`` / ``_D``) are not part of this
-build and are refused with a ValueError.
+the depth-map variants (``cheng2020-attn_R`` / ``_D``) are not part of this build and are refused with a
+ValueError; so is ``ssf2020``: the video model itself is built (``compressai.models.video.ScaleSpaceFlow``, whose
+``update(force=True)`` fills its six CDF buffer sets), but this command line stays image-only like ``eval_model``
+and ``codec_rgbt``, whose video branches are not built either.
 """
 from __future__ import annotations
 

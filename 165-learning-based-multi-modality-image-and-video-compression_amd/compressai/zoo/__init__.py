@@ -3,6 +3,7 @@ from .pretrained import load_pretrained
 from .pretrained import load_pretrained as load_state_dict
 from .image import (bmshj2018_factorized, bmshj2018_hyperprior, cfgs, cheng2020_anchor, cheng2020_attn, mbt2018,
                     mbt2018_mean, model_architectures)
+from .video import ssf2020
 
 image_models = {
     "bmshj2018-factorized": bmshj2018_factorized,
@@ -13,6 +14,12 @@ image_models = {
     "cheng2020-attn": cheng2020_attn,
 }
 
-models = dict(image_models)
+video_models = {
+    "ssf2020": ssf2020,
+}
 
-__all__ = ["image_models", "models", "cfgs", "model_architectures", "load_state_dict", "load_pretrained"]
+models = dict(image_models)
+models.update(video_models)
+
+__all__ = ["image_models", "video_models", "models", "cfgs", "model_architectures", "load_state_dict",
+           "load_pretrained"]

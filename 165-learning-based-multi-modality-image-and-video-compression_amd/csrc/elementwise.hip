@@ -10,9 +10,11 @@
 //   pixel shuffle / its inverse (torch.nn.PixelShuffle channel order c*r^2 + i*r + j)
 //   gdn1 out     y = x / norm  (inverse: x * norm)    GDN1.forward after its |x| 1x1 conv, gdn.py:111-121
 //   gdn1 bwd     dx = g / norm, dnorm = -g x / norm^2  (inverse: g norm, g x)
+//   qrelu        y = clamp(x, 0, 2^bits - 1) and its smoothed backward (layers.py QReLU)
 #include "common.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <initializer_list>
 
 namespace cai {
@@ -289,6 +291,45 @@ __global__ void axpy_dev_kernel(int64_t n, const float* __restrict__ x, const fl
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] += x[i] * s;
 }
 
+// QReLU (layers/layers.py: the integer-network activation of the video hyperprior's scale decoder)
+//   fwd   y = clamp(x, 0, vmax), vmax = 2^bit_depth - 1
+//   bwd   dx = g inside [0, vmax]; outside dx = g exp(-alpha^beta |u|^beta), u = 2 x / vmax - 1.  Outside the range
+//         |u| = 1 + d with d = -2 x / vmax (x < 0) or 2 (x - vmax) / vmax (x > vmax), so |u|^beta = exp(beta log1p(d))
+//         keeps d's bits; lab = beta log(alpha) comes from the host in double.
+__device__ __forceinline__ float qrelu_grad_f(float x, float g, float vmax, float beta, float lab) {
+    if (x >= 0.f && x <= vmax) return g;
+    const float d = x < 0.f ? -2.f * x / vmax : 2.f * (x - vmax) / vmax;
+    return g * expf(-expf(fmaf(beta, log1pf(d), lab)));
+}
+
+template <typename T, int BWD>
+__global__ void qrelu_kernel(const T* __restrict__ x, int xld, const T* __restrict__ g, int gld, T* __restrict__ y,
+                             int yld, int npix, int C, float vmax, float beta, float lab) {
+    constexpr int N = Vec<T>::N;
+    const int nch = (C + N - 1) / N;
+    const int64_t total = (int64_t)npix * nch;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i / nch), c0 = (int)(i - (int64_t)p * nch) * N;
+        if (c0 + N <= C) {
+            const typename Vec<T>::V vx = *reinterpret_cast<const typename Vec<T>::V*>(x + (int64_t)p * xld + c0);
+            typename Vec<T>::V vg, vy;
+            if (BWD) vg = *reinterpret_cast<const typename Vec<T>::V*>(g + (int64_t)p * gld + c0);
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                const float v = to_f32(vx[e]);
+                vy[e] = from_f32<T>(BWD ? qrelu_grad_f(v, to_f32(vg[e]), vmax, beta, lab) : fminf(fmaxf(v, 0.f), vmax));
+            }
+            *reinterpret_cast<typename Vec<T>::V*>(y + (int64_t)p * yld + c0) = vy;
+        } else {
+            for (int c = c0; c < C; ++c) {
+                const float v = to_f32(x[(int64_t)p * xld + c]);
+                y[(int64_t)p * yld + c] = from_f32<T>(BWD ? qrelu_grad_f(v, to_f32(g[(int64_t)p * gld + c]), vmax, beta, lab)
+                                                          : fminf(fmaxf(v, 0.f), vmax));
+            }
+        }
+    }
+}
+
 static int ew_grid2(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(16384, (n + 255) / 256)); }
 
 }  // namespace cai
@@ -455,6 +496,58 @@ int cai_pixel_shuffle(int dtype, const void* src, const int64_t* src_strides, vo
     else
         hipLaunchKernelGGL(pixel_shuffle_kernel<float>, dim3(ew_grid2(n)), dim3(256), 0, st, s);
     CAI_LAUNCH_CHECK("pixel_shuffle");
+    return CAI_OK;
+}
+
+static int qrelu_check(const char* what, int dtype, const void* x, int32_t x_ld, const void* y, int32_t y_ld,
+                       int64_t npix, int32_t C, int32_t bit_depth) {
+    CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "%s: bad dtype", what);
+    CAI_CHECK_ARG(x && y, "%s: null pointer", what);
+    CAI_CHECK_ARG(C >= 1 && x_ld >= C && y_ld >= C && npix >= 0 && npix < (1ll << 31), "%s: bad shape", what);
+    CAI_CHECK_ARG(bit_depth >= 1 && bit_depth <= 16, "%s: bit_depth %d outside 1..16", what, bit_depth);
+    const int N = dtype == CAI_BF16 ? 8 : 4;
+    CAI_CHECK_ARG(x_ld % N == 0 && y_ld % N == 0, "%s: ld must be a multiple of %d", what, N);
+    return CAI_OK;
+}
+
+int cai_qrelu_fwd(int dtype, const void* x, int32_t x_ld, void* y, int32_t y_ld, int64_t npix, int32_t C,
+                  int32_t bit_depth, void* stream) {
+    int rc = qrelu_check("qrelu_fwd", dtype, x, x_ld, y, y_ld, npix, C, bit_depth);
+    if (rc != CAI_OK) return rc;
+    const int N = dtype == CAI_BF16 ? 8 : 4;
+    const int64_t n = npix * ((C + N - 1) / N);
+    if (n == 0) return CAI_OK;
+    const float vmax = (float)((1 << bit_depth) - 1);
+    hipStream_t st = as_stream(stream);
+    if (dtype == CAI_BF16)
+        hipLaunchKernelGGL((qrelu_kernel<bf16, 0>), dim3(ew_grid2(n)), dim3(256), 0, st, (const bf16*)x, x_ld,
+                           (const bf16*)nullptr, 0, (bf16*)y, y_ld, (int)npix, C, vmax, 0.f, 0.f);
+    else
+        hipLaunchKernelGGL((qrelu_kernel<float, 0>), dim3(ew_grid2(n)), dim3(256), 0, st, (const float*)x, x_ld,
+                           (const float*)nullptr, 0, (float*)y, y_ld, (int)npix, C, vmax, 0.f, 0.f);
+    CAI_LAUNCH_CHECK("qrelu_fwd");
+    return CAI_OK;
+}
+
+int cai_qrelu_bwd(int dtype, const void* x, int32_t x_ld, const void* g, int32_t g_ld, void* dx, int32_t dx_ld,
+                  int64_t npix, int32_t C, int32_t bit_depth, float beta, void* stream) {
+    int rc = qrelu_check("qrelu_bwd", dtype, x, x_ld, dx, dx_ld, npix, C, bit_depth);
+    if (rc != CAI_OK) return rc;
+    const int N = dtype == CAI_BF16 ? 8 : 4;
+    CAI_CHECK_ARG(g && g_ld >= C && g_ld % N == 0, "qrelu_bwd: bad upstream gradient");
+    CAI_CHECK_ARG(beta > 0.f, "qrelu_bwd: beta must be positive");
+    const int64_t n = npix * ((C + N - 1) / N);
+    if (n == 0) return CAI_OK;
+    const float vmax = (float)((1 << bit_depth) - 1);
+    const float lab = (float)((double)beta * std::log(0.9943258522851727));
+    hipStream_t st = as_stream(stream);
+    if (dtype == CAI_BF16)
+        hipLaunchKernelGGL((qrelu_kernel<bf16, 1>), dim3(ew_grid2(n)), dim3(256), 0, st, (const bf16*)x, x_ld,
+                           (const bf16*)g, g_ld, (bf16*)dx, dx_ld, (int)npix, C, vmax, beta, lab);
+    else
+        hipLaunchKernelGGL((qrelu_kernel<float, 1>), dim3(ew_grid2(n)), dim3(256), 0, st, (const float*)x, x_ld,
+                           (const float*)g, g_ld, (float*)dx, dx_ld, (int)npix, C, vmax, beta, lab);
+    CAI_LAUNCH_CHECK("qrelu_bwd");
     return CAI_OK;
 }
 

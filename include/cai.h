@@ -800,6 +800,40 @@ int cai_act_bwd(int mask_mode, float param, const void* y, int32_t y_ld, const v
                 void* out, int32_t out_ld, int64_t npix, int32_t C, int dtype, void* stream);
 int cai_cast(const void* x, int x_dtype, void* y, int y_dtype, int64_t n, void* stream);
 
+/* QReLU (layers/layers.py, the video hyperprior's scale decoder) on pixel-major activations, bf16 / fp32:
+ * y = clamp(x, 0, 2^bit_depth - 1); dx = g inside the range, g exp(-alpha^beta |2 x / max - 1|^beta) outside,
+ * alpha = 0.9943258522851727.  bit_depth 1..16, ld a multiple of 4 (fp32) / 8 (bf16). */
+int cai_qrelu_fwd(int dtype, const void* x, int32_t x_ld, void* y, int32_t y_ld, int64_t npix, int32_t C,
+                  int32_t bit_depth, void* stream);
+int cai_qrelu_bwd(int dtype, const void* x, int32_t x_ld, const void* g, int32_t g_ld, void* dx, int32_t dx_ld,
+                  int64_t npix, int32_t C, int32_t bit_depth, float beta, void* stream);
+
+/* =======================================================================
+ * Scale-space motion compensation of ScaleSpaceFlow (csrc/ssf.hip).  fp32, dense planes.
+ * ======================================================================= */
+/* Gaussian volume of `planes` images [planes][H][W] (planes = N * C): volume [planes][levels + 1][H][W].  Slice 0
+ * is x, slice 1 its blur with the normalised Gaussian of 2 ceil(3 sigma) + 1 taps (at most 31) and replicate
+ * padding; slice l >= 2 is blur(avg_pool2x2(previous blurred image)) brought back to H x W by l - 1 bilinear x2
+ * steps (align_corners = false).  H and W must be multiples of 2^(levels - 1).  Both directions need a workspace of
+ * cai_ssf_workspace_bytes (0 = bad shape).  The backward is the exact adjoint, without atomics. */
+size_t cai_ssf_workspace_bytes(int32_t planes, int32_t H, int32_t W, int32_t levels);
+int cai_ssf_volume_fwd(const float* x, int32_t planes, int32_t H, int32_t W, float sigma, int32_t levels,
+                       float* volume, void* workspace, size_t ws_bytes, void* stream);
+int cai_ssf_volume_bwd(const float* dvolume, int32_t planes, int32_t H, int32_t W, float sigma, int32_t levels,
+                       float* dx, void* workspace, size_t ws_bytes, void* stream);
+/* Trilinear warp of volume [N][C][D][H][W] (grid_sample, padding_mode = "border", align_corners = false) at
+ * ix = w + flow_x W / 2, iy = h + flow_y H / 2, iz = ((scale + 1) D - 1) / 2.  motion holds (flow_x, flow_y,
+ * scale) as [N][3][H][W] read through motion_strides[4] (elements: n, c, h, w).  x_pred [N][C][H][W]; with x_cur
+ * the same launch also writes x_res = x_cur - x_pred (both null or both set). */
+int cai_ssf_warp_fwd(const float* volume, const float* motion, const int64_t* motion_strides, int32_t N, int32_t C,
+                     int32_t D, int32_t H, int32_t W, float* x_pred, const float* x_cur, float* x_res, void* stream);
+/* Upstream gradient g = g_pred - g_res (either nullable).  d_motion [N][3][H][W] dense (nullable): zero where a
+ * coordinate was clamped.  d_volume (nullable) must be zeroed by the caller; it is filled by a launch of its own
+ * with fp32 atomic adds, so its low bits depend on the order of the adds. */
+int cai_ssf_warp_bwd(const float* volume, const float* motion, const int64_t* motion_strides, int32_t N, int32_t C,
+                     int32_t D, int32_t H, int32_t W, const float* g_pred, const float* g_res, float* d_motion,
+                     float* d_volume, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
