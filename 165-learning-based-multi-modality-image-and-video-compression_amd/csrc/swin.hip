@@ -642,8 +642,9 @@ extern "C" {
 int cai_layernorm_fwd(int dtype, const void* x, int32_t x_ld, int64_t ntok, int32_t C, const float* w, const float* b,
                       float eps, void* y, int32_t y_ld, float* mean, float* rstd, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "layernorm_fwd: bad dtype");
-    CAI_CHECK_ARG(x && w && b && y && mean && rstd && C > 0 && C <= 1024 && x_ld >= C && y_ld >= C &&
-                      ntok < (1ll << 31), "layernorm_fwd: bad arguments");
+    CAI_CHECK_ARG(x && w && b && y && mean && rstd && C > 0 && C <= 1024 && ntok >= 0 && ntok < (1ll << 31),
+                  "layernorm_fwd: bad arguments");
+    CAI_CHECK_ARG(x_ld >= C && y_ld >= C, "layernorm_fwd: row pitches (x_ld %d, y_ld %d) below C = %d", x_ld, y_ld, C);
     if (ntok == 0) return CAI_OK;
     DISPATCH_T(dtype, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3((unsigned)((ntok + 3) / 4)), dim3(256), 0,
                                          as_stream(stream), (const T*)x, x_ld, (int)ntok, C, w, b, eps, (T*)y, y_ld,
@@ -670,8 +671,10 @@ int cai_layernorm_bwd(int dtype, const void* x, int32_t x_ld, const void* dy, in
                       const float* w, const float* mean, const float* rstd, void* dx, int32_t dx_ld, float* dw,
                       float* db, int32_t accumulate, void* workspace, size_t ws_bytes, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "layernorm_bwd: bad dtype");
-    CAI_CHECK_ARG(x && dy && w && mean && rstd && dx && C > 0 && C <= 1024 && ntok < (1ll << 31),
+    CAI_CHECK_ARG(x && dy && w && mean && rstd && dx && C > 0 && C <= 1024 && ntok >= 0 && ntok < (1ll << 31),
                   "layernorm_bwd: bad arguments");
+    CAI_CHECK_ARG(x_ld >= C && dy_ld >= C && dx_ld >= C,
+                  "layernorm_bwd: row pitches (x_ld %d, dy_ld %d, dx_ld %d) below C = %d", x_ld, dy_ld, dx_ld, C);
     CAI_CHECK_ARG(workspace && ws_bytes >= cai_layernorm_bwd_workspace_bytes(ntok, C), "layernorm_bwd: workspace");
     if (ntok == 0) return CAI_OK;
     const int nblk = (int)std::min<int64_t>(1024, (ntok + 63) / 64);
@@ -695,7 +698,8 @@ int cai_layernorm_bwd(int dtype, const void* x, int32_t x_ld, const void* dy, in
 
 int cai_gelu_fwd(int dtype, const void* x, int32_t x_ld, void* y, int32_t y_ld, int64_t ntok, int32_t C, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "gelu_fwd: bad dtype");
-    CAI_CHECK_ARG(x && y && x_ld >= C && y_ld >= C && ntok < (1ll << 31), "gelu_fwd: bad arguments");
+    CAI_CHECK_ARG(x && y && C > 0 && ntok >= 0 && ntok < (1ll << 31), "gelu_fwd: bad arguments");
+    CAI_CHECK_ARG(x_ld >= C && y_ld >= C, "gelu_fwd: row pitches (x_ld %d, y_ld %d) below C = %d", x_ld, y_ld, C);
     if (dtype == CAI_BF16 && vec8_ok(C, {x_ld, y_ld}, {x, y})) {
         hipLaunchKernelGGL(gelu_fwd_vec_kernel, dim3(grid256(ntok * C / 8)), dim3(256), 0, as_stream(stream),
                            (const bf16*)x, x_ld, (bf16*)y, y_ld, (int)ntok, C);
@@ -711,7 +715,9 @@ int cai_gelu_fwd(int dtype, const void* x, int32_t x_ld, void* y, int32_t y_ld, 
 int cai_gelu_bwd(int dtype, const void* x, int32_t x_ld, const void* g, int32_t g_ld, void* dx, int32_t dx_ld,
                  int64_t ntok, int32_t C, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "gelu_bwd: bad dtype");
-    CAI_CHECK_ARG(x && g && dx && ntok < (1ll << 31), "gelu_bwd: bad arguments");
+    CAI_CHECK_ARG(x && g && dx && C > 0 && ntok >= 0 && ntok < (1ll << 31), "gelu_bwd: bad arguments");
+    CAI_CHECK_ARG(x_ld >= C && g_ld >= C && dx_ld >= C,
+                  "gelu_bwd: row pitches (x_ld %d, g_ld %d, dx_ld %d) below C = %d", x_ld, g_ld, dx_ld, C);
     if (dtype == CAI_BF16 && vec8_ok(C, {x_ld, g_ld, dx_ld}, {x, g, dx})) {
         hipLaunchKernelGGL(gelu_bwd_vec_kernel, dim3(grid256(ntok * C / 8)), dim3(256), 0, as_stream(stream),
                            (const bf16*)x, x_ld, (const bf16*)g, g_ld, (bf16*)dx, dx_ld, (int)ntok, C);
@@ -731,6 +737,10 @@ static int check_attn(const cai_window_attn* p) {
     CAI_CHECK_ARG(p->Hr % WS == 0 && p->Wr % WS == 0 && p->B > 0, "window_attn: resolution must be a multiple of 4");
     CAI_CHECK_ARG(p->shift >= 0 && p->shift < WS, "window_attn: bad shift");
     CAI_CHECK_ARG(p->q && p->kv && p->bias_table && p->rel_index, "window_attn: null pointer");
+    CAI_CHECK_ARG(p->Hr > 0 && p->Wr > 0 && (int64_t)p->B * p->Hr * p->Wr < (1ll << 31), "window_attn: bad token grid");
+    CAI_CHECK_ARG(p->q_ld >= p->heads * HD && p->kv_ld >= 2 * p->heads * HD,
+                  "window_attn: row pitches (q_ld %d, kv_ld %d) below heads * head_dim = %d (q) / twice that (kv)",
+                  p->q_ld, p->kv_ld, p->heads * HD);
     return CAI_OK;
 }
 
@@ -752,6 +762,8 @@ int cai_window_attn_fwd(int dtype, const cai_window_attn* p, void* out, int32_t 
     if (rc) return rc;
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "window_attn_fwd: bad dtype");
     CAI_CHECK_ARG(out, "window_attn_fwd: null output");
+    CAI_CHECK_ARG(out_ld >= p->heads * HD, "window_attn_fwd: out_ld %d below heads * head_dim = %d", out_ld,
+                  p->heads * HD);
     AttnArgs a = attn_args(p);
     a.o = out; a.o_ld = out_ld;
     DISPATCH_T(dtype, hipLaunchKernelGGL(window_attn_fwd_kernel<T>, dim3(attn_blocks(p)), dim3(256), 0,
@@ -773,6 +785,9 @@ int cai_window_attn_bwd(int dtype, const cai_window_attn* p, const void* dout, i
     if (rc) return rc;
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "window_attn_bwd: bad dtype");
     CAI_CHECK_ARG(dout && dq && dkv && dbias_table, "window_attn_bwd: null pointer");
+    CAI_CHECK_ARG(dout_ld >= p->heads * HD && dq_ld >= p->heads * HD && dkv_ld >= 2 * p->heads * HD,
+                  "window_attn_bwd: row pitches (dout_ld %d, dq_ld %d, dkv_ld %d) below heads * head_dim = %d "
+                  "(dout, dq) / twice that (dkv)", dout_ld, dq_ld, dkv_ld, p->heads * HD);
     CAI_CHECK_ARG(workspace && ws_bytes >= cai_window_attn_bwd_workspace_bytes(p), "window_attn_bwd: workspace");
     AttnArgs a = attn_args(p);
     a.dout = dout; a.dout_ld = dout_ld; a.dq = dq; a.dq_ld = dq_ld; a.dkv = dkv; a.dkv_ld = dkv_ld;
@@ -803,6 +818,8 @@ int cai_channel_mean(int dtype, const void* x, int32_t x_ld, const void* x2, int
                      int32_t C, float* out, float scale, void* workspace, size_t ws_bytes, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "channel_mean: bad dtype");
     CAI_CHECK_ARG(x && out && B > 0 && HW > 0 && HW < (1ll << 31) && C > 0, "channel_mean: bad arguments");
+    CAI_CHECK_ARG(x_ld >= C && (!x2 || x2_ld >= C), "channel_mean: row pitches (x_ld %d, x2_ld %d) below C = %d", x_ld,
+                  x2 ? x2_ld : x_ld, C);
     const int vec = dtype == CAI_BF16 ? 8 : 4;
     CAI_CHECK_ARG(C <= 256 * vec && x_ld % vec == 0 && ((uintptr_t)x & 15) == 0 &&
                       (!x2 || (x2_ld % vec == 0 && ((uintptr_t)x2 & 15) == 0)),
@@ -823,7 +840,9 @@ int cai_channel_mean(int dtype, const void* x, int32_t x_ld, const void* x2, int
 int cai_channel_affine(int dtype, const void* x, int32_t x_ld, const float* gamma, const float* beta, float beta_scale,
                        void* y, int32_t y_ld, int32_t B, int64_t HW, int32_t C, void* stream) {
     CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "channel_affine: bad dtype");
-    CAI_CHECK_ARG(y && B > 0 && HW > 0 && C > 0 && (!gamma || x), "channel_affine: bad arguments");
+    CAI_CHECK_ARG(y && B > 0 && HW > 0 && HW < (1ll << 31) && C > 0 && (!gamma || x), "channel_affine: bad arguments");
+    CAI_CHECK_ARG(y_ld >= C && (!gamma || x_ld >= C), "channel_affine: row pitches (x_ld %d, y_ld %d) below C = %d",
+                  gamma ? x_ld : y_ld, y_ld, C);
     if (dtype == CAI_BF16 && vec8_ok(C, {gamma ? x_ld : 8, y_ld}, {gamma ? x : nullptr, y})) {
         hipLaunchKernelGGL(channel_affine_vec_kernel, dim3(grid256((int64_t)B * HW * C / 8)), dim3(256), 0,
                            as_stream(stream), (const bf16*)x, x_ld, gamma, beta, (bf16*)y, y_ld, B, (int)HW, C,

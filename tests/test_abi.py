@@ -169,3 +169,78 @@ def test_halo_kernel_selection(native):
     assert "halo" not in name(G(4, 192, 64, 64, 192, 64, 64, 3, 1, 1, 0, 0), 0)
     assert lib.cai_conv_kernel_name(ctypes.byref(G(4, 192, 128, 128, 192, 128, 128, 3, 1, 1, 0, 0)), native.F32,
                                     0, 0).decode().startswith("conv_gemm")
+
+
+# ---- csrc/swin.hip: every row pitch must hold its row -----------------------------------------------------------
+_NN = ctypes.c_void_p(4096)      # non-null, never dereferenced: validation precedes any device work
+
+
+def _attn(native, heads=3, q_ld=None, kv_ld=None, **kw):
+    f = dict(B=1, Hr=8, Wr=8, head_dim=32, window=4, shift=0)
+    f.update(kw)
+    return native.WindowAttn(_NN, heads * 32 if q_ld is None else q_ld, _NN, 2 * heads * 32 if kv_ld is None else kv_ld,
+                             _NN, _NN, None, f["B"], f["Hr"], f["Wr"], heads, f["head_dim"], f["window"], f["shift"],
+                             0.25)
+
+
+def _swin_bad_calls(native):
+    """(name, call returning the status, expected fragment of the message)."""
+    lib = native.lib.load()
+    F, BF = native.F32, native.BF16
+    big = 1 << 30
+    ok, P = _attn(native), ctypes.byref
+    return [
+        ("ln_fwd x_ld", lambda: lib.cai_layernorm_fwd(F, _NN, 95, 8, 96, _NN, _NN, 1e-5, _NN, 96, _NN, _NN, None), b"pitch"),
+        ("ln_fwd y_ld", lambda: lib.cai_layernorm_fwd(F, _NN, 96, 8, 96, _NN, _NN, 1e-5, _NN, 95, _NN, _NN, None), b"pitch"),
+        ("ln_fwd ntok", lambda: lib.cai_layernorm_fwd(F, _NN, 96, -1, 96, _NN, _NN, 1e-5, _NN, 96, _NN, _NN, None), b"bad"),
+        ("ln_bwd x_ld", lambda: lib.cai_layernorm_bwd(F, _NN, 95, _NN, 96, 8, 96, _NN, _NN, _NN, _NN, 96, None, None, 0,
+                                                      _NN, big, None), b"pitch"),
+        ("ln_bwd dy_ld", lambda: lib.cai_layernorm_bwd(F, _NN, 96, _NN, 95, 8, 96, _NN, _NN, _NN, _NN, 96, None, None, 0,
+                                                       _NN, big, None), b"pitch"),
+        ("ln_bwd dx_ld", lambda: lib.cai_layernorm_bwd(BF, _NN, 96, _NN, 96, 8, 96, _NN, _NN, _NN, _NN, 0, None, None, 0,
+                                                       _NN, big, None), b"pitch"),
+        ("ln_bwd ntok", lambda: lib.cai_layernorm_bwd(F, _NN, 96, _NN, 96, -4, 96, _NN, _NN, _NN, _NN, 96, None, None, 0,
+                                                      _NN, big, None), b"bad"),
+        ("gelu_fwd y_ld", lambda: lib.cai_gelu_fwd(BF, _NN, 16, _NN, 8, 4, 16, None), b"pitch"),
+        ("gelu_fwd ntok", lambda: lib.cai_gelu_fwd(BF, _NN, 16, _NN, 16, -1, 16, None), b"bad"),
+        ("gelu_bwd x_ld", lambda: lib.cai_gelu_bwd(BF, _NN, 8, _NN, 16, _NN, 16, 4, 16, None), b"pitch"),
+        ("gelu_bwd g_ld", lambda: lib.cai_gelu_bwd(F, _NN, 16, _NN, 15, _NN, 16, 4, 16, None), b"pitch"),
+        ("gelu_bwd dx_ld", lambda: lib.cai_gelu_bwd(F, _NN, 16, _NN, 16, _NN, -16, 4, 16, None), b"pitch"),
+        ("gelu_bwd ntok", lambda: lib.cai_gelu_bwd(F, _NN, 16, _NN, 16, _NN, 16, -1, 16, None), b"bad"),
+        ("mean x_ld", lambda: lib.cai_channel_mean(F, _NN, 8, None, 0, 1, 64, 12, _NN, 1.0, _NN, big, None), b"pitch"),
+        ("mean x2_ld", lambda: lib.cai_channel_mean(F, _NN, 12, _NN, 8, 1, 64, 12, _NN, 1.0, _NN, big, None), b"pitch"),
+        ("mean HW", lambda: lib.cai_channel_mean(F, _NN, 12, None, 0, 1, -64, 12, _NN, 1.0, _NN, big, None), b"bad"),
+        ("affine x_ld", lambda: lib.cai_channel_affine(BF, _NN, 8, _NN, _NN, 1.0, _NN, 16, 1, 64, 16, None), b"pitch"),
+        ("affine y_ld", lambda: lib.cai_channel_affine(BF, None, 0, None, _NN, 1.0, _NN, 8, 1, 64, 16, None), b"pitch"),
+        ("affine HW", lambda: lib.cai_channel_affine(F, _NN, 16, _NN, _NN, 1.0, _NN, 16, 1, -1, 16, None), b"bad"),
+        ("attn q_ld", lambda: lib.cai_window_attn_fwd(F, P(_attn(native, q_ld=95)), _NN, 96, None), b"pitch"),
+        ("attn kv_ld", lambda: lib.cai_window_attn_fwd(F, P(_attn(native, kv_ld=96)), _NN, 96, None), b"pitch"),
+        ("attn heads 8 kv_ld", lambda: lib.cai_window_attn_fwd(BF, P(_attn(native, heads=8, kv_ld=511)), _NN, 256, None),
+         b"pitch"),
+        ("attn head_dim", lambda: lib.cai_window_attn_fwd(F, P(_attn(native, head_dim=16)), _NN, 96, None), b"head_dim"),
+        ("attn out_ld", lambda: lib.cai_window_attn_fwd(F, P(ok), _NN, 64, None), b"out_ld"),
+        ("attn dout_ld", lambda: lib.cai_window_attn_bwd(F, P(ok), _NN, 95, _NN, 96, _NN, 192, _NN, 0, _NN, big, None),
+         b"pitch"),
+        ("attn dq_ld", lambda: lib.cai_window_attn_bwd(F, P(ok), _NN, 96, _NN, 32, _NN, 192, _NN, 0, _NN, big, None),
+         b"pitch"),
+        ("attn dkv_ld", lambda: lib.cai_window_attn_bwd(F, P(ok), _NN, 96, _NN, 96, _NN, 96, _NN, 0, _NN, big, None),
+         b"pitch"),
+        ("attn bwd q_ld", lambda: lib.cai_window_attn_bwd(F, P(_attn(native, q_ld=0)), _NN, 96, _NN, 96, _NN, 192, _NN,
+                                                          0, _NN, big, None), b"pitch"),
+    ]
+
+
+def test_swin_pitches_below_the_row_width_are_einval(native):
+    """A pitch below the row width would make rows overlap silently: every such call of the LayerNorm, GELU,
+    window-attention and channel-aligner entry points is refused with a message.  The pointers are not device
+    memory and the test runs without a GPU, so a call that got past validation to a launch could not return
+    CAI_EINVAL."""
+    lib = native.lib.load()
+    for name, call, fragment in _swin_bad_calls(native):
+        rc = call()
+        msg = lib.cai_last_error()
+        assert rc == native.CAI_EINVAL, (name, rc, msg)
+        assert msg and fragment in msg, (name, msg)
+    bad = _attn(native, kv_ld=100)
+    assert lib.cai_window_attn_bwd_workspace_bytes(ctypes.byref(bad)) == 0
+    assert lib.cai_window_attn_bwd_workspace_bytes(ctypes.byref(_attn(native))) == (3 + 65) * 3 * 256 * 4
