@@ -240,6 +240,10 @@ SIGNATURES = {
     "cai_ssf_warp_fwd": (_I, [_P, _P, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "cai_ssf_warp_bwd": (_I, [_P, _P, POINTER(c_int64), c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
                               _P]),
+    "cai_yuv420_to_rgb": (_I, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, c_int32,
+                               _P, _P]),
+    "cai_video_frame_sse": (_I, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32,
+                                 _P, _P, _P]),
 }
 
 

@@ -2754,3 +2754,66 @@ class ScaleSpaceWarpFn(torch.autograd.Function):
         if has_cur and ctx.needs_input_grad[2]:
             dcur = gr
         return (dv, None if dm is None else dm.to(mdtype), dcur)
+
+
+# ---------------------------------------------------------------------------
+# Raw YUV 4:2:0 frames around the video codec (utils/video/frames.py) -- csrc/video.hip
+# ---------------------------------------------------------------------------
+
+VIDEO_UPSAMPLING = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+
+
+def _check_yuv420(planes, bitdepth):
+    """Three contiguous device planes in the container the kernels read: uint8 at 8 bits, 16-bit words above."""
+    if len(planes) != 3:
+        raise ValueError("expected the three planes (y, u, v)")
+    y, u, v = planes
+    _check_cuda(y, u, v)
+    if y.dim() != 2 or y.shape[0] % 2 or y.shape[1] % 2:
+        raise ValueError(f"4:2:0 needs an even [H, W] luma plane, got {tuple(y.shape)}")
+    H, W = y.shape
+    want = torch.uint8 if int(bitdepth) == 8 else (torch.int16, torch.uint16)
+    for name, t, shape in (("y", y, (H, W)), ("u", u, (H // 2, W // 2)), ("v", v, (H // 2, W // 2))):
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"plane {name}: expected a contiguous {shape} tensor, got {tuple(t.shape)}")
+        if t.dtype != want and not (isinstance(want, tuple) and t.dtype in want):
+            raise ValueError(f"plane {name}: dtype {t.dtype} is not the {bitdepth}-bit container")
+    return H, W
+
+
+def yuv420_to_rgb(planes, bitdepth: int, mode: str, Hp: int, Wp: int, top: int, left: int):
+    """Integer planes (y [H, W], u, v [H/2, W/2]) -> (x fp32 [1, 3, Hp, Wp]: BT.709 RGB at (top, left), zero
+    around it; org_q fp32 [3, H, W]: x's levels rint(clamp(x max_val, 0, max_val))).  One launch."""
+    H, W = _check_yuv420(planes, bitdepth)
+    if mode not in VIDEO_UPSAMPLING:
+        raise ValueError(f'Invalid upsampling mode "{mode}".')
+    y, u, v = planes
+    x = torch.empty((1, 3, Hp, Wp), dtype=torch.float32, device=y.device)
+    org_q = torch.empty((3, H, W), dtype=torch.float32, device=y.device)
+    _ledger.run(lambda: lib.cai_yuv420_to_rgb(_p(y), _p(u), _p(v), H, W, int(bitdepth), VIDEO_UPSAMPLING[mode], _p(x),
+                                              Hp, Wp, top, left, _p(org_q), _stream()),
+                "yuv420_to_rgb", "yuv420_to_rgb_kernel", 0,
+                4 * (x.numel() + org_q.numel()) + 3 * y.numel() * y.element_size() // 2, torch.float32)
+    return x, org_q
+
+
+def video_frame_sse(planes, bitdepth: int, org_q, rec, top: int, left: int):
+    """(int64 [4]: the sums of squared level differences of Y, U, V and RGB between the frame and the
+    reconstruction rec fp32 [1, 3, Hp, Wp]; rec_q fp32 [3, H, W]: the reconstruction's RGB levels).  A memset and
+    one launch; nothing is read back."""
+    H, W = _check_yuv420(planes, bitdepth)
+    y, u, v = planes
+    _check_cuda(org_q, rec)
+    if tuple(org_q.shape) != (3, H, W) or org_q.dtype != torch.float32 or not org_q.is_contiguous():
+        raise ValueError(f"org_q must be a contiguous fp32 [3, {H}, {W}] tensor")
+    if rec.dim() != 4 or rec.shape[0] != 1 or rec.shape[1] != 3:
+        raise ValueError(f"the reconstruction must be [1, 3, Hp, Wp], got {tuple(rec.shape)}")
+    rec = rec.float().contiguous()
+    Hp, Wp = rec.shape[-2:]
+    sums = torch.zeros(4, dtype=torch.int64, device=y.device)
+    rec_q = torch.empty((3, H, W), dtype=torch.float32, device=y.device)
+    _ledger.run(lambda: lib.cai_video_frame_sse(_p(y), _p(u), _p(v), H, W, int(bitdepth), _p(org_q), _p(rec), Hp, Wp,
+                                                top, left, _p(sums), _p(rec_q), _stream()),
+                "video_frame_sse", "video_frame_sse_kernel", 0, 4 * 9 * H * W + 3 * y.numel() * y.element_size() // 2,
+                torch.float32)
+    return sums, rec_q

@@ -834,6 +834,30 @@ int cai_ssf_warp_bwd(const float* volume, const float* motion, const int64_t* mo
                      int32_t D, int32_t H, int32_t W, const float* g_pred, const float* g_res, float* d_motion,
                      float* d_volume, void* stream);
 
+/* =======================================================================
+ * Raw YUV 4:2:0 frames around the video codec (csrc/video.hip).  Planes are contiguous planar Y [H][W], U and V
+ * [H/2][W/2] on the device: uint8 at bitdepth 8, little-endian uint16 at 10 / 12 / 14 / 16.  H and W even, >= 2.
+ * The frame sits at (top, left) of a padded Hp x Wp image.  CAI_EINVAL (before any device work) for null pointers,
+ * odd or small H / W, another bit depth, negative padding or a frame that does not fit, an unknown mode.
+ * ======================================================================= */
+/* rgb fp32 [3][Hp][Wp]: the frame as BT.709 RGB in [0, 1] (up to the chroma filter's overshoot), zero around it,
+ * all written by one launch.  Samples are normalised by the division c / (2^bitdepth - 1); the chroma is upsampled
+ * x2 with align_corners = false semantics, mode 0 nearest, 1 bilinear, 2 bicubic (A = -0.75: output 2k reads
+ * k - 2 .. k + 1 with weights -0.03515625, 0.26171875, 0.87890625, -0.10546875, output 2k + 1 the mirrored set on
+ * k - 1 .. k + 2; tap indices clamp to the plane).  org_q (nullable) fp32 [3][H][W]:
+ * rint(clamp(rgb max_val, 0, max_val)), integer-valued. */
+int cai_yuv420_to_rgb(const void* y, const void* u, const void* v, int32_t H, int32_t W, int32_t bitdepth,
+                      int32_t mode, float* rgb, int32_t Hp, int32_t Wp, int32_t top, int32_t left, float* org_q,
+                      void* stream);
+/* rec fp32 [3][Hp][Wp] is clamped to [0, 1]; rec_q (nullable) fp32 [3][H][W] = rint(clamp(rec max_val, 0, max_val)).
+ * sums[4] += the sums of squared level differences of Y, U, V (BT.709 RGB -> YCbCr, 2 x 2 mean of the chroma,
+ * rounded to levels, against the integer planes) and of RGB (rec_q against org_q, the output of the call above).
+ * Integer accumulation, one 64-bit atomic add per block and sum: bit-reproducible.  The caller zeroes sums on the
+ * same stream. */
+int cai_video_frame_sse(const void* y, const void* u, const void* v, int32_t H, int32_t W, int32_t bitdepth,
+                        const float* org_q, const float* rec, int32_t Hp, int32_t Wp, int32_t top, int32_t left,
+                        uint64_t* sums, float* rec_q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

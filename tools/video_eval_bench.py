@@ -1,0 +1,173 @@
+"""The per-frame path of the raw-video evaluation outside the model, at 1920x1080: the fused HIP path of
+compressai.utils.video.frames (two launches of csrc/video.hip + the MS-SSIM op) against the torch body of the same
+module on GPU tensors (the reference driver's composition: true division, two bicubic interpolate, cat, ycbcr2rgb,
+pad; crop, rgb2ycbcr, two avg_pool2d, four clamp-round-square-sum groups; the same MS-SSIM op), both behind the same
+upload of the integer planes.  For scale: one encode_inter of ssf2020(1) at 1920x1152.
+
+Steps: frames8, frames10 (the A/B at 8 and 10 bits), model.  With --step all (the default) every step runs in a
+child process of its own under its own time limit, and the first failure ends the run.  A frame step prints, per
+path, the host-clock time of the whole per-frame path (upload .. metrics, ending in a device synchronise) as mean
++- standard deviation over rounds that alternate between the paths, and the device time of the pieces between events.
+usage: python tools/video_eval_bench.py [--step all|frames8|frames10|model] [--rounds 7] [--iters 20]"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("165-learning-based-multi-modality-image-and-video-compression_amd", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+H, W = 1080, 1920
+LIMITS = {"frames8": 240, "frames10": 240, "model": 420}      # seconds per step
+
+
+def frame_record(bitdepth, seed=0):
+    import numpy as np
+
+    import video_reference as R
+
+    planes = R.moving_clip(H, W, 1, bitdepth, seed)[0]
+    kind = np.uint8 if bitdepth == 8 else np.uint16
+    rec = np.zeros((), dtype=np.dtype([("y", kind, (H, W)), ("u", kind, (H // 2, W // 2)), ("v", kind, (H // 2, W // 2))]))
+    for name, p in zip("yuv", planes):
+        rec[name] = p.astype(kind)
+    return rec
+
+
+def frames_step(bitdepth, rounds, iters):
+    import torch
+
+    from compressai.utils.metrics import ms_ssim
+    from compressai.utils.video import frames
+
+    dev = torch.device("cuda:0")
+    max_val = 2 ** bitdepth - 1
+    rec = frame_record(bitdepth)
+    _, _, padding = frames.pad_geometry(H, W, 128)
+    planes0 = frames.to_planes(rec, dev)
+    x0, _, org_q0 = frames.yuv420_to_rgb(planes0, bitdepth, "bicubic", 128)
+    x_rec = (x0 + 0.02 * torch.randn(x0.shape, generator=torch.Generator().manual_seed(1)).to(dev)).clamp_(0, 1)
+
+    def torch_metrics(planes, org_q):
+        sums, rec_q = frames.frame_sse_torch(planes, org_q, x_rec, padding, bitdepth)
+        return sums, ms_ssim(org_q[None], rec_q[None], data_range=float(max_val))
+
+    def fused():
+        planes = frames.to_planes(rec, dev)
+        x, _, org_q = frames.yuv420_to_rgb(planes, bitdepth, "bicubic", 128)
+        return x, frames.frame_metrics(planes, org_q, x_rec, padding, bitdepth)
+
+    def aten():
+        planes = frames.to_planes(rec, dev)
+        x, org_q = frames.yuv420_to_rgb_torch(planes, bitdepth, "bicubic", padding)
+        return x, torch_metrics(planes, org_q)
+
+    pieces = {
+        "upload": lambda: frames.to_planes(rec, dev),
+        "to_rgb hip": lambda: frames.yuv420_to_rgb(planes0, bitdepth, "bicubic", 128),
+        "to_rgb torch": lambda: frames.yuv420_to_rgb_torch(planes0, bitdepth, "bicubic", padding),
+        "sse hip": lambda: frames.frame_sse(planes0, org_q0, x_rec, padding, bitdepth),
+        "sse torch": lambda: frames.frame_sse_torch(planes0, org_q0, x_rec, padding, bitdepth),
+        "ms-ssim op": lambda: ms_ssim(org_q0[None], org_q0[None] * 0.99, data_range=float(max_val)),
+    }
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / iters
+
+    def device(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / iters
+
+    print(f"per-frame path outside the model, {W}x{H} {bitdepth} bit -> {W}x{H + padding[2] + padding[3]}, bicubic, "
+          f"{rounds} rounds x {iters} iters")
+    xf, mf = fused()
+    xa, (sa, _) = aten()
+    sf = frames.frame_sse(planes0, org_q0, x_rec, padding, bitdepth)
+    print(f"  max |x hip - x torch| {(xf - xa).abs().max().item():.2e}; sums hip {sf.tolist()} torch {sa.tolist()}; "
+          f"psnr-yuv {mf['psnr-yuv'].item():.3f} ms-ssim-rgb {mf['ms-ssim-rgb'].item():.6f}")
+    paths = {"hip": fused, "torch": aten}
+    for fn in list(paths.values()) + list(pieces.values()):
+        for _ in range(3):
+            fn()
+    us = {p: [] for p in paths}
+    for _ in range(rounds):
+        for p, fn in paths.items():
+            us[p].append(wall(fn))
+    mh, mt = statistics.mean(us["hip"]), statistics.mean(us["torch"])
+    print(f"  whole path (host clock, upload .. metrics): hip {mh:8.1f} +- {statistics.stdev(us['hip']):6.1f} us   "
+          f"torch {mt:8.1f} +- {statistics.stdev(us['torch']):6.1f} us   torch / hip {mt / mh:.2f}x")
+    for name, fn in pieces.items():
+        t = [device(fn) for _ in range(rounds)]
+        print(f"  {name:13s} (device events) {statistics.mean(t):8.1f} +- {statistics.stdev(t):6.1f} us")
+
+
+def model_step(rounds):
+    import torch
+
+    from compressai.zoo import ssf2020
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    net = ssf2020(1).to(dev).eval()
+    net.update(force=True)
+    g = torch.Generator().manual_seed(0)
+    x_ref = torch.rand(1, 3, 1152, W, generator=g).to(dev)
+    x_cur = (x_ref + 0.02 * torch.randn(1, 3, 1152, W, generator=g).to(dev)).clamp_(0, 1)
+    with torch.no_grad():
+        for _ in range(2):
+            net.encode_inter(x_cur, x_ref)
+        ms = []
+        for _ in range(rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            net.encode_inter(x_cur, x_ref)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+    print(f"ssf2020(1).encode_inter at {W}x1152 fp32 (transforms + entropy coding, host clock): "
+          f"{statistics.mean(ms):.1f} +- {statistics.stdev(ms):.1f} ms over {rounds} calls")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=("all", "frames8", "frames10", "model"), default="all")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=20)
+    args = ap.parse_args()
+    if args.step == "all":
+        for step, limit in LIMITS.items():
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--rounds", str(args.rounds), "--iters",
+                   str(args.iters)]
+            try:
+                rc = subprocess.run(cmd, timeout=limit).returncode
+            except subprocess.TimeoutExpired:
+                print(f"step {step} ran past its limit of {limit} s; stopping", flush=True)
+                raise SystemExit(124)
+            if rc != 0:
+                print(f"step {step} ended with status {rc}; stopping", flush=True)
+                raise SystemExit(rc if rc > 0 else 1)
+        return
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("video_eval_bench: no GPU is visible; nothing is measured without one")
+    if args.step == "model":
+        model_step(args.rounds)
+    else:
+        frames_step(8 if args.step == "frames8" else 10, args.rounds, args.iters)
+
+
+if __name__ == "__main__":
+    main()
