@@ -244,6 +244,7 @@ SIGNATURES = {
                                _P, _P]),
     "cai_video_frame_sse": (_I, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32,
                                  _P, _P, _P]),
+    "cai_rgb_to_yuv420": (_I, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
 }
 
 

@@ -2817,3 +2817,27 @@ def video_frame_sse(planes, bitdepth: int, org_q, rec, top: int, left: int):
                 "video_frame_sse", "video_frame_sse_kernel", 0, 4 * 9 * H * W + 3 * y.numel() * y.element_size() // 2,
                 torch.float32)
     return sums, rec_q
+
+
+def rgb_to_yuv420(rec, bitdepth: int, H: int, W: int, top: int, left: int):
+    """Reconstruction rec fp32 [1, 3, Hp, Wp] -> the H x W frame at (top, left) as one device buffer of H W 3 / 2
+    samples in file order (Y [H][W], U [H/2][W/2], V): uint8 at 8 bits, unsigned 16-bit words in an int16 tensor
+    above.  The levels are those video_frame_sse measures: rec clamped to [0, 1], BT.709 RGB -> YCbCr, 2 x 2 mean
+    of the chroma, rint(clamp(. max_val, 0, max_val)).  One launch."""
+    _check_cuda(rec)
+    if rec.dim() != 4 or rec.shape[0] != 1 or rec.shape[1] != 3:
+        raise ValueError(f"the reconstruction must be [1, 3, Hp, Wp], got {tuple(rec.shape)}")
+    bitdepth, H, W, top, left = int(bitdepth), int(H), int(W), int(top), int(left)
+    if bitdepth not in (8, 10, 12, 14, 16):
+        raise ValueError(f"bit depth {bitdepth} not in (8, 10, 12, 14, 16)")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 needs even H and W, got {H} x {W}")
+    Hp, Wp = rec.shape[-2:]
+    if top < 0 or left < 0 or top + H > Hp or left + W > Wp:
+        raise ValueError(f"the {H} x {W} frame at ({top}, {left}) does not fit the padded {Hp} x {Wp} image")
+    rec = rec.float().contiguous()
+    out = torch.empty(H * W * 3 // 2, dtype=torch.uint8 if bitdepth == 8 else torch.int16, device=rec.device)
+    _ledger.run(lambda: lib.cai_rgb_to_yuv420(_p(rec), Hp, Wp, top, left, H, W, bitdepth, _p(out), _stream()),
+                "rgb_to_yuv420", "rgb_to_yuv420_kernel", 0, 4 * 3 * H * W + out.numel() * out.element_size(),
+                torch.float32)
+    return out

@@ -1,7 +1,7 @@
-"""The multi-modal bit-stream container and its image encode / decode CLI (reference: examples/codec_rgbt.py:
-141-386, 454-555, 607-830).
+"""The multi-modal bit-stream container and its encode / decode CLI for images and, with ``--model ssf2020``, raw
+YUV 4:2:0 video (reference: examples/codec_rgbt.py:141-830).
 
-File layout, all integers big-endian (codec_rgbt.py:188-250, 328-386):
+Image file layout, all integers big-endian (codec_rgbt.py:188-250, 328-386):
 
     u8  model id             index of the architecture in the reference's model registry (``MODEL_IDS``)
     u8  code                 metric << 4 | (quality - 1) & 0x0F
@@ -18,6 +18,23 @@ holds the master's bits only.
     python -m compressai.utils.codec_rgbt encode IMG --model Master_compresser --path G.pth M.pth -ch 3 -o out.bin
     python -m compressai.utils.codec_rgbt decode out.bin --model Master_compresser --path G.pth M.pth \
         -ch 3 --guided GUIDE_IMG -o rec.png
+
+Video file layout (codec_rgbt.py:389-451, 557-598), big-endian:
+
+    u8  model id (6: ssf2020), u8 code
+    u32 height, u32 width, u8 bitdepth, u32 frames
+    per frame one body (the keyframe) or two (motion, residual), a body as above
+
+After the first two bytes this is the container ``compressai.utils.video.eval_model`` writes; its header, body and
+frame-loop code is used here, so the two tools produce the same bytes.  The input is a raw planar 4:2:0 ``.yuv``
+file whose name states size, rate and depth; the decoder writes a ``.yuv`` file of the same layout (any other suffix:
+the last frame as an image).  A decoded frame becomes integer planes in one launch (``frames.rgb_to_yuv420``) with
+the levels rounded to nearest, the rounding the evaluation's metrics use -- the reference truncates here -- so the
+PSNR of a decoded file against its source is the PSNR ``eval_model`` reports for the stream.
+
+    python -m compressai.utils.codec_rgbt encode clip_1920x1080_30fps_420_8bit.yuv --model ssf2020 --path S.pth \
+        [-f FRAMES] -o clip.bin
+    python -m compressai.utils.codec_rgbt decode clip.bin --model ssf2020 --path S.pth -o rec_1920x1080_8bit.yuv
 """
 from __future__ import annotations
 
@@ -274,6 +291,104 @@ def decode_image(inputpath: str, net, guided: Optional[torch.Tensor] = None) -> 
     return hdr, crop(x_hat, hdr.original_size)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# video (codec_rgbt.py:389-451, 557-598): the two header bytes, then the container of utils/video/eval_model
+
+VIDEO_MODELS = ("ssf2020",)
+
+
+class VideoHeader(NamedTuple):
+    model: str
+    metric: str
+    quality: int
+    original_size: Tuple[int, int]
+    bitdepth: int
+    frames: int
+
+
+def _container():
+    """The module that owns the video container and the frame loops (imported late: it pulls in the models)."""
+    from compressai.utils.video.eval_model import __main__ as container
+
+    return container
+
+
+def write_video_header(fd: IO[bytes], metric: str, quality: int, height: int, width: int, bitdepth: int, frames: int,
+                       model: str = "ssf2020") -> int:
+    if model not in VIDEO_MODELS:
+        raise ValueError(f'"{model}" is not a video model')
+    return write_uchars(fd, get_header(model, metric, quality)) + _container().write_header(fd, height, width,
+                                                                                            bitdepth, frames)
+
+
+def read_video_header(fd: IO[bytes]) -> VideoHeader:
+    model, metric, quality = parse_header(read_uchars(fd, 2))
+    if model not in VIDEO_MODELS:
+        raise ValueError(f"stream was coded with {model}, which is not a video model")
+    height, width, bitdepth, frames = _container().read_header(fd)
+    return VideoHeader(model, metric, quality, (height, width), bitdepth, frames)
+
+
+def encode_video(input: str, net, output: str, metric: str = "mse", quality: int = 3,
+                 num_frames: int = -1) -> Dict[str, float]:
+    """Code the first ``num_frames`` frames (all if negative) of the raw 4:2:0 file ``input`` into ``output``.
+    Returns the file's bpp, the frame count and the mean encoding time per frame (codec_rgbt.py:389-451)."""
+    if Path(input).suffix != ".yuv":
+        raise NotImplementedError(f"Unsupported video file extension: {Path(input).suffix}")
+    container = _container()
+    org_seq = container._open(input)
+    if num_frames < 0:
+        num_frames = len(org_seq)
+    if num_frames > len(org_seq):
+        raise ValueError(f"{num_frames} frames asked for, {input} holds {len(org_seq)}")
+    stamps = [time.time()]
+    with Path(output).open("wb") as f:
+        write_uchars(f, get_header("ssf2020", metric, quality))
+        container.encode_frames(net, org_seq, f, num_frames, per_frame=lambda *_: stamps.append(time.time()))
+    h, w = org_seq.height, org_seq.width
+    org_seq.close()
+    return {"bpp": Path(output).stat().st_size * 8.0 / (h * w * max(num_frames, 1)), "frames": num_frames,
+            "avg_frm_enc_time": (stamps[-1] - stamps[0]) / max(num_frames, 1)}
+
+
+def decode_video(inputpath: str, net, output: Optional[str] = None) -> Tuple[VideoHeader, Optional[torch.Tensor]]:
+    """Decode ``inputpath``.  With ``output`` ending in .yuv every frame is appended to it as integer 4:2:0 planes
+    (one launch and one copy per frame, levels rounded to nearest); any other ``output`` receives the last frame as
+    an image.  Returns the header and the last frame [1, C, H, W] in [0, 1] (codec_rgbt.py:557-598)."""
+    from compressai.utils.video import frames
+
+    container = _container()
+    to_yuv = output is not None and Path(output).suffix == ".yuv"
+    last: List[torch.Tensor] = []
+    with Path(inputpath).open("rb") as f:
+        hdr = read_video_header(f)
+        h, w = hdr.original_size
+        fout = Path(output).open("wb") if to_yuv else None
+        try:
+            def emit(i, x_rec, padding):
+                if fout is not None:
+                    frames.write_frame(fout, frames.rgb_to_yuv420(x_rec, padding, hdr.bitdepth), hdr.bitdepth)
+                if i == hdr.frames - 1:
+                    last.append(container.crop(x_rec, padding, h, w))
+
+            container.decode_frames(net, f, h, w, hdr.frames, emit)
+        finally:
+            if fout is not None:
+                fout.close()
+    x_hat = last[0] if last else None
+    if output is not None and not to_yuv and x_hat is not None:
+        torch2img(x_hat).save(output)
+    return hdr, x_hat
+
+
+def _load_video_net(model: str, paths: Sequence[str], device):
+    if len(paths) != 1:
+        raise ValueError(f"{model} takes one checkpoint")
+    net = _container().load_checkpoint(model, paths[0]).to(device)
+    net.update(force=True)
+    return net
+
+
 def _device(args) -> str:
     """This build's kernels are GPU-only: the CLIs always use the GPU and fail up front without one."""
     if not torch.cuda.is_available():
@@ -314,16 +429,18 @@ def _common_args(p: argparse.ArgumentParser):
 
 
 def encode_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Encode an image to a bit-stream")
+    p = argparse.ArgumentParser(description="Encode an image, or a raw 4:2:0 video with a video model, to a bit-stream")
     p.add_argument("input")
     p.add_argument("-m", "--metric", choices=list(METRIC_IDS), default="mse")
     p.add_argument("-q", "--quality", type=int, default=3)
+    p.add_argument("-f", "--num_of_frames", type=int, default=-1,
+                   help="video: how many frames to code (default: all of them)")
     _common_args(p)
     return p
 
 
 def decode_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Decode a bit-stream to an image")
+    p = argparse.ArgumentParser(description="Decode a bit-stream to an image, or to a raw 4:2:0 video")
     p.add_argument("input")
     _common_args(p)
     return p
@@ -335,6 +452,11 @@ def encode(argv):
     a = encode_parser().parse_args(argv)
     compressai.set_entropy_coder(a.coder)
     device = _device(a)
+    if a.model in VIDEO_MODELS:
+        net = _load_video_net(a.model, a.path, device)
+        r = encode_video(a.input, net, a.output, a.metric, a.quality, a.num_of_frames)
+        print(f"{r['bpp']:.3f} bpp | {r['frames']} frames | {r['avg_frm_enc_time']:.2f}s per frame")
+        return
     net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)
     x = load_master_image(a.input, a.channel, device)
     guided = None
@@ -350,7 +472,16 @@ def decode(argv):
 
     a = decode_parser().parse_args(argv)
     compressai.set_entropy_coder(a.coder)
+    with Path(a.input).open("rb") as f:
+        coded_with = parse_header(read_uchars(f, 2))[0]
+    if (coded_with in VIDEO_MODELS or a.model in VIDEO_MODELS) and coded_with != a.model:
+        raise ValueError(f"{a.input} was coded with {coded_with}, not with --model {a.model}")
     device = _device(a)
+    if a.model in VIDEO_MODELS:
+        t = time.time()
+        hdr, _ = decode_video(a.input, _load_video_net(a.model, a.path, device), a.output)
+        print(f"Decoded {hdr.frames} frames in {time.time() - t:.2f}s")
+        return
     net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)
     guided = None
     if a.model == "Master_compresser":

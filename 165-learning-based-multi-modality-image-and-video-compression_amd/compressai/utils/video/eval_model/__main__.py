@@ -159,16 +159,15 @@ def _finish(results: Dict[str, list]) -> Dict[str, float]:
 
 
 @torch.no_grad()
-def eval_model(net: nn.Module, sequence: Path, binpath: Path, keep_binaries: bool = False,
-               half: bool = False) -> Dict[str, Any]:
-    """Code ``sequence`` into ``binpath``; the metrics of the encoder's reconstructions and the file's bit rate."""
-    sequence, binpath = Path(sequence), Path(binpath)
-    org_seq = _open(sequence)
+def encode_frames(net: nn.Module, org_seq: RawVideoSequence, f, num_frames: int, half: bool = False,
+                  per_frame=None) -> None:
+    """Write the container of the first ``num_frames`` frames of ``org_seq`` to the open file ``f``: the header, then
+    each frame's bodies.  ``per_frame(i, planes, org_q, x_rec, padding)`` is called after frame i is written, with
+    its integer planes on the device, its RGB levels and the clamped reconstruction (the next reference: it must
+    not be changed).  The one encoder loop of this package: the evaluation and the codec CLI both run it."""
     device = next(net.parameters()).device
-    num_frames, bitdepth = len(org_seq), org_seq.bitdepth
-    results = defaultdict(list)
-    print(f" encoding {sequence.stem}", file=sys.stderr)
-    with binpath.open("wb") as f, prepacked_forward(net):
+    bitdepth = org_seq.bitdepth
+    with prepacked_forward(net):
         write_header(f, org_seq.height, org_seq.width, bitdepth, num_frames)
         x_rec = None
         for i in range(num_frames):
@@ -183,8 +182,26 @@ def eval_model(net: nn.Module, sequence: Path, binpath: Path, keep_binaries: boo
                     for key in ("motion", "residual"):
                         write_body(f, enc_info["shape"][key], enc_info["strings"][key])
             x_rec = x_rec.float().clamp_(0, 1)
-            for k, v in frames.frame_metrics(planes, org_q, x_rec, padding, bitdepth).items():
-                results[k].append(v)
+            if per_frame is not None:
+                per_frame(i, planes, org_q, x_rec, padding)
+
+
+@torch.no_grad()
+def eval_model(net: nn.Module, sequence: Path, binpath: Path, keep_binaries: bool = False,
+               half: bool = False) -> Dict[str, Any]:
+    """Code ``sequence`` into ``binpath``; the metrics of the encoder's reconstructions and the file's bit rate."""
+    sequence, binpath = Path(sequence), Path(binpath)
+    org_seq = _open(sequence)
+    num_frames, bitdepth = len(org_seq), org_seq.bitdepth
+    results = defaultdict(list)
+
+    def measure(i, planes, org_q, x_rec, padding):
+        for k, v in frames.frame_metrics(planes, org_q, x_rec, padding, bitdepth).items():
+            results[k].append(v)
+
+    print(f" encoding {sequence.stem}", file=sys.stderr)
+    with binpath.open("wb") as f:
+        encode_frames(net, org_seq, f, num_frames, half, measure)
     seq_results: Dict[str, Any] = _finish(results)
     seq_results["bitrate"] = float(filesize(binpath)) * 8 * float(org_seq.framerate) / (num_frames * 1000)
     if not keep_binaries:
@@ -222,14 +239,13 @@ def eval_model_entropy_estimation(net: nn.Module, sequence: Path, half: bool = F
 
 
 @torch.no_grad()
-def decode_sequence(net: nn.Module, binpath: Path, half: bool = False) -> List[torch.Tensor]:
-    """The frames a bitstream written by ``eval_model`` decodes to: [1, 3, H, W] each, cropped and clamped to
-    [0, 1] (the clamped, uncropped frame is the next reference, as on the encoder side)."""
+def decode_frames(net: nn.Module, f, height: int, width: int, num_frames: int, per_frame, half: bool = False) -> None:
+    """Decode the ``num_frames`` frames that follow the header in the open file ``f``.  ``per_frame(i, x_rec,
+    padding)`` is called with each clamped, still padded reconstruction (the next reference: it must not be
+    changed) and the (left, right, top, bottom) of the frame inside it."""
     device = next(net.parameters()).device
-    out = []
-    with Path(binpath).open("rb") as f, prepacked_forward(net):
-        height, width, _, num_frames = read_header(f)
-        Hp, Wp, (left, _, top, _) = frames.pad_geometry(height, width, net.downsampling_factor)
+    Hp, Wp, padding = frames.pad_geometry(height, width, net.downsampling_factor)
+    with prepacked_forward(net):
         x_rec = None
         for i in range(num_frames):
             with _autocast(half, device):
@@ -243,7 +259,23 @@ def decode_sequence(net: nn.Module, binpath: Path, half: bool = False) -> List[t
             x_rec = x_rec.float().clamp_(0, 1)
             if tuple(x_rec.shape[-2:]) != (Hp, Wp):
                 raise ValueError(f"frame {i} decodes to {tuple(x_rec.shape[-2:])}, the header says {Hp} x {Wp} padded")
-            out.append(x_rec[:, :, top:top + height, left:left + width].clone())
+            per_frame(i, x_rec, padding)
+
+
+def crop(x_rec: torch.Tensor, padding, height: int, width: int) -> torch.Tensor:
+    left, _, top, _ = padding
+    return x_rec[:, :, top:top + height, left:left + width].clone()
+
+
+@torch.no_grad()
+def decode_sequence(net: nn.Module, binpath: Path, half: bool = False) -> List[torch.Tensor]:
+    """The frames a bitstream written by ``eval_model`` decodes to: [1, 3, H, W] each, cropped and clamped to
+    [0, 1] (the clamped, uncropped frame is the next reference, as on the encoder side)."""
+    out = []
+    with Path(binpath).open("rb") as f:
+        height, width, _, num_frames = read_header(f)
+        decode_frames(net, f, height, width, num_frames,
+                      lambda i, x_rec, padding: out.append(crop(x_rec, padding, height, width)), half)
     return out
 
 

@@ -3,10 +3,12 @@
 Into the model: ``yuv420_to_rgb`` turns the integer planes of one frame into the zero-padded fp32 RGB model input
 and the RGB levels ``org_q`` the metrics compare against.  Out of the model: ``frame_metrics`` turns the
 reconstruction into PSNR-Y/U/V/YUV, MSE / PSNR-RGB and MS-SSIM-RGB, all as 0-dim device tensors -- nothing here
-reads back to the host, the driver does that once per sequence.
+reads back to the host, the driver does that once per sequence.  Out of the decoder: ``rgb_to_yuv420`` turns the
+reconstruction into the integer 4:2:0 frame, with the levels the metrics measure, as one buffer in file order, and
+``write_frame`` appends it to a raw file (utils/codec_rgbt.py).
 
-On GPU tensors each direction is one launch of csrc/video.hip (``_ops.yuv420_to_rgb`` / ``_ops.video_frame_sse``)
-plus the MS-SSIM op; the squared level differences are integers and are summed as integers, so the sums do not
+On GPU tensors each direction is one launch of csrc/video.hip (``_ops.yuv420_to_rgb`` / ``_ops.video_frame_sse`` /
+``_ops.rgb_to_yuv420``) plus the MS-SSIM op; the squared level differences are integers and are summed as integers, so the sums do not
 depend on any order.  On CPU tensors the ``*_torch`` bodies below spell out the same formulas in fp32 with torch
 ops: the composition the reference's driver runs (true division, ``interpolate``, ``cat``, ``ycbcr2rgb``, ``pad``
 / crop, ``rgb2ycbcr``, two ``avg_pool2d``, clamp-round per plane).  They also run on GPU tensors, which is what
@@ -23,7 +25,7 @@ from ...transforms.functional import rgb2ycbcr, ycbcr2rgb, yuv_420_to_444, yuv_4
 from ..metrics import ms_ssim
 
 __all__ = ["to_planes", "pad_geometry", "yuv420_to_rgb", "frame_sse", "frame_metrics", "yuv420_to_rgb_torch",
-           "frame_sse_torch"]
+           "frame_sse_torch", "rgb_to_yuv420", "rgb_to_yuv420_torch", "write_frame"]
 
 BITDEPTHS = (8, 10, 12, 14, 16)
 MODES = ("nearest", "bilinear", "bicubic")
@@ -168,6 +170,81 @@ def _sse(planes, org_q, x_rec, padding, bitdepth):
 
         return _ops.video_frame_sse(tuple(_container(p, bitdepth) for p in planes), bitdepth, org_q, x_rec, top, left)
     return frame_sse_torch(planes, org_q, x_rec, padding, bitdepth)
+
+
+class FramePlanes(tuple):
+    """(y, u, v) of one written frame.  ``buffer`` is the flat tensor of H W 3 / 2 samples in file order that the
+    three planes are views of: a frame goes to the host, and to a file, in one copy."""
+
+    def __new__(cls, buffer: torch.Tensor, H: int, W: int):
+        n = H * W
+        if buffer.dim() != 1 or buffer.numel() != n * 3 // 2:
+            raise ValueError(f"a {H} x {W} 4:2:0 frame holds {n * 3 // 2} samples, got {tuple(buffer.shape)}")
+        self = super().__new__(cls, (buffer[:n].view(H, W), buffer[n:n + n // 4].view(H // 2, W // 2),
+                                     buffer[n + n // 4:].view(H // 2, W // 2)))
+        self.buffer = buffer
+        return self
+
+
+def _check_rec(x_rec, padding, bitdepth: int):
+    if bitdepth not in BITDEPTHS:
+        raise ValueError(f"bit depth {bitdepth} not in {BITDEPTHS}")
+    if len(padding) != 4 or any(int(p) != p or p < 0 for p in padding):
+        raise ValueError(f"padding must be four non-negative integers (left, right, top, bottom), got {padding}")
+    if not isinstance(x_rec, torch.Tensor) or x_rec.dim() != 4 or tuple(x_rec.shape[:2]) != (1, 3):
+        got = tuple(x_rec.shape) if isinstance(x_rec, torch.Tensor) else type(x_rec).__name__
+        raise ValueError(f"the reconstruction must be [1, 3, Hp, Wp], got {got}")
+    left, right, top, bottom = (int(p) for p in padding)
+    H, W = x_rec.shape[2] - top - bottom, x_rec.shape[3] - left - right
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"4:2:0 needs even H and W, got {H} x {W}")
+    return H, W, top, left
+
+
+def rgb_to_yuv420_torch(x_rec, padding, bitdepth: int) -> FramePlanes:
+    H, W, _, _ = _check_rec(x_rec, padding, bitdepth)
+    max_val = 2 ** bitdepth - 1
+    rec = F.pad(x_rec.float(), tuple(-int(p) for p in padding)).clamp(0, 1)
+    levels = [(r[0, 0] * max_val).clamp(0, max_val).round().reshape(-1)
+              for r in yuv_444_to_420(rgb2ycbcr(rec), mode="avg_pool")]
+    return FramePlanes(_container(torch.cat(levels).to(torch.int32), bitdepth), H, W)
+
+
+def rgb_to_yuv420(x_rec, padding, bitdepth: int) -> FramePlanes:
+    """The reconstruction ``x_rec`` [1, 3, Hp, Wp] (any float dtype; clamped to [0, 1] here) -> the integer 4:2:0
+    frame inside ``padding`` (left, right, top, bottom): (y [H, W], u, v [H/2, W/2]), uint8 at 8 bits and unsigned
+    words in int16 tensors above, views of one buffer in file order (``.buffer``).  The levels are the ones
+    ``frame_sse`` measures: BT.709 RGB -> YCbCr, 2 x 2 chroma mean, rounded to nearest.  On the GPU one launch.  A
+    wrong shape, odd H or W or another bit depth raises ValueError before any launch."""
+    H, W, top, left = _check_rec(x_rec, padding, bitdepth)
+    if x_rec.is_cuda:
+        from ... import _ops
+
+        return FramePlanes(_ops.rgb_to_yuv420(x_rec, bitdepth, H, W, top, left), H, W)
+    return rgb_to_yuv420_torch(x_rec, padding, bitdepth)
+
+
+def write_frame(fout, planes_or_buffer, bitdepth: int) -> int:
+    """Append one frame to the open binary file ``fout`` as raw planar samples: Y, U, V, one byte each at 8 bits,
+    little-endian 16-bit words above.  Takes what ``rgb_to_yuv420`` returns (one copy to the host), its flat buffer,
+    or any three integer planes.  Returns the bytes written."""
+    if bitdepth not in BITDEPTHS:
+        raise ValueError(f"bit depth {bitdepth} not in {BITDEPTHS}")
+    if isinstance(planes_or_buffer, FramePlanes):
+        parts = [planes_or_buffer.buffer]
+    elif isinstance(planes_or_buffer, torch.Tensor):
+        parts = [planes_or_buffer]
+    else:
+        parts = list(to_planes(planes_or_buffer))
+    n = 0
+    for t in parts:
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("the samples must be integers")
+        a = _container(t, bitdepth).cpu().numpy()
+        data = a.tobytes() if bitdepth == 8 else a.view(np.uint16).astype("<u2", copy=False).tobytes()
+        fout.write(data)
+        n += len(data)
+    return n
 
 
 def frame_sse(planes, org_q, x_rec, padding, bitdepth: int) -> torch.Tensor:

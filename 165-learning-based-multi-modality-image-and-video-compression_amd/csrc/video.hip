@@ -1,5 +1,6 @@
 // The per-frame path around the video codec when it is evaluated on raw YUV 4:2:0 (utils/video/eval_model): two
-// launches per frame, fp32 arithmetic, integer planes in, exact integer error sums out.
+// launches per frame, fp32 arithmetic, integer planes in, exact integer error sums out; and, when it decodes to a raw
+// file (utils/codec_rgbt), one launch per frame from the reconstruction to integer planes.
 //
 // yuv420 -> rgb    integer planar Y [H][W], U, V [H/2][W/2] (uint8 at 8 bits, uint16 above) -> fp32 planar RGB
 //                  [3][Hp][Wp], the frame at (top, left) and zero around it: the model input.  Every sample is
@@ -16,6 +17,11 @@
 //                  and RGB (rec_q against org_q).  The differences are integers, so they are summed as integers:
 //                  per thread, per wave, per block, then one 64-bit atomic add per block and sum.  Integer
 //                  addition is order-free: the sums are bit-reproducible with no fixed-order reduce.
+// rgb -> yuv420    reconstruction [3][Hp][Wp] at the same offsets -> the integer frame in file order, Y [H][W] then U
+//                  and V [H/2][W/2] in one buffer (uint8 at 8 bits, uint16 above): the decoder's output, one copy and
+//                  one write away from a .yuv file.  The levels come from the device function the frame sse measures
+//                  (vid_quad_levels), so a written file has exactly the PSNR that was reported.  One thread per quad,
+//                  plain vector stores, nothing shared.
 #include <algorithm>
 
 #include "common.hpp"
@@ -72,6 +78,28 @@ __device__ __forceinline__ void vid_chroma_quad(const T* __restrict__ p, int h, 
 }
 
 __device__ __forceinline__ float vid_level(float v, float mv) { return rintf(fminf(fmaxf(v * mv, 0.f), mv)); }
+
+__device__ __forceinline__ float vid_clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+
+// One 2 x 2 quad of the clamped reconstruction, c[channel][pixel], as 4:2:0 levels: BT.709 RGB -> YCbCr, the four Y
+// and the quad's mean Cb and Cr, rounded.  The frame-sse kernel measures these levels and the writer stores them:
+// one body, so what is written is what was measured.  The luma sum KR r + KG g + KB b is the one expression here
+// that the compiler may contract, and how it does so depends on the code around the call (the writer got a packed
+// multiply and a plain add where the frame-sse kernel has two fused steps): the fused steps are therefore spelled
+// out, in the form the frame-sse kernel has always been compiled to -- the rounded green product first.
+__device__ __forceinline__ void vid_quad_levels(const float (&c)[3][4], float mv, float (&yq)[4], float& uq,
+                                                float& vq) {
+    float cbs = 0.f, crs = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float y = fmaf(VID_KB, c[2][k], fmaf(VID_KR, c[0][k], VID_KG * c[1][k]));
+        cbs += 0.5f * (c[2][k] - y) / VID_1_KB + 0.5f;
+        crs += 0.5f * (c[0][k] - y) / VID_1_KR + 0.5f;
+        yq[k] = vid_level(y, mv);
+    }
+    uq = vid_level(cbs * 0.25f, mv);
+    vq = vid_level(crs * 0.25f, mv);
+}
 
 struct vid_geom {
     int32_t H, W, Hp, Wp, top, left;
@@ -198,7 +226,7 @@ __global__ __launch_bounds__(256) void video_frame_sse_kernel(const T* __restric
             float q[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                c[ch][k] = fminf(fmaxf(c[ch][k], 0.f), 1.f);
+                c[ch][k] = vid_clamp01(c[ch][k]);
                 q[k] = vid_level(c[ch][k], mv);
                 acc[3] += vid_sq(q[k], oq[k]);
             }
@@ -214,16 +242,12 @@ __global__ __launch_bounds__(256) void video_frame_sse_kernel(const T* __restric
         }
         const T* yr = Y + (int64_t)fy * g.W + fx;
         const float yo[4] = {(float)yr[0], (float)yr[1], (float)yr[g.W], (float)yr[g.W + 1]};
-        float cbs = 0.f, crs = 0.f;
+        float yq[4], uq, vq;
+        vid_quad_levels(c, mv, yq, uq, vq);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float y = VID_KR * c[0][k] + VID_KG * c[1][k] + VID_KB * c[2][k];
-            cbs += 0.5f * (c[2][k] - y) / VID_1_KB + 0.5f;
-            crs += 0.5f * (c[0][k] - y) / VID_1_KR + 0.5f;
-            acc[0] += vid_sq(vid_level(y, mv), yo[k]);
-        }
-        acc[1] += vid_sq(vid_level(cbs * 0.25f, mv), (float)U[(int64_t)ky * hw2 + kx]);
-        acc[2] += vid_sq(vid_level(crs * 0.25f, mv), (float)V[(int64_t)ky * hw2 + kx]);
+        for (int k = 0; k < 4; ++k) acc[0] += vid_sq(yq[k], yo[k]);
+        acc[1] += vid_sq(uq, (float)U[(int64_t)ky * hw2 + kx]);
+        acc[2] += vid_sq(vq, (float)V[(int64_t)ky * hw2 + kx]);
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
@@ -236,6 +260,48 @@ __global__ __launch_bounds__(256) void video_frame_sse_kernel(const T* __restric
         const unsigned long long s =
             (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
         if (s) atomicAdd(sums + threadIdx.x, s);
+    }
+}
+
+template <typename T> struct alignas(2 * sizeof(T)) vid_pair { T a, b; };
+
+// VEC & 1: left and Wp even and rec 8-byte aligned, so a quad's row is one aligned float2.  VEC & 2: out aligned to
+// two samples, so the two Y levels of a row (W and fx are even) are one aligned two-sample store.
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const float* __restrict__ rec, const vid_geom g, float mv,
+                                                            T* __restrict__ out) {
+    const int hw2 = g.W >> 1;
+    const int64_t quads = (int64_t)(g.H >> 1) * hw2;
+    const int64_t ps = (int64_t)g.Hp * g.Wp, fs = (int64_t)g.H * g.W;
+    T* U = out + fs;      // file order: Y [H][W], U [H/2][W/2], V
+    T* V = U + quads;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < quads; i += (int64_t)gridDim.x * 256) {
+        const int ky = (int)(i / hw2), kx = (int)(i % hw2);
+        const int fy = 2 * ky, fx = 2 * kx;
+        float c[3][4];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float* s = rec + ch * ps + (int64_t)(g.top + fy) * g.Wp + g.left + fx;
+            if (VEC & 1) {
+                const float2 a = *reinterpret_cast<const float2*>(s), b = *reinterpret_cast<const float2*>(s + g.Wp);
+                c[ch][0] = a.x, c[ch][1] = a.y, c[ch][2] = b.x, c[ch][3] = b.y;
+            } else {
+                c[ch][0] = s[0], c[ch][1] = s[1], c[ch][2] = s[g.Wp], c[ch][3] = s[g.Wp + 1];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[ch][k] = vid_clamp01(c[ch][k]);
+        }
+        float yq[4], uq, vq;
+        vid_quad_levels(c, mv, yq, uq, vq);
+        T* d = out + (int64_t)fy * g.W + fx;     // levels are integers in [0, 65535]
+        if (VEC & 2) {
+            *reinterpret_cast<vid_pair<T>*>(d) = vid_pair<T>{(T)(int)yq[0], (T)(int)yq[1]};
+            *reinterpret_cast<vid_pair<T>*>(d + g.W) = vid_pair<T>{(T)(int)yq[2], (T)(int)yq[3]};
+        } else {
+            d[0] = (T)(int)yq[0], d[1] = (T)(int)yq[1], d[g.W] = (T)(int)yq[2], d[g.W + 1] = (T)(int)yq[3];
+        }
+        U[i] = (T)(int)uq;
+        V[i] = (T)(int)vq;
     }
 }
 
@@ -339,6 +405,38 @@ int cai_video_frame_sse(const void* y, const void* u, const void* v, int32_t H, 
     }
 #undef CAI_SSE_LAUNCH
     CAI_LAUNCH_CHECK("video_frame_sse");
+    return CAI_OK;
+}
+
+int cai_rgb_to_yuv420(const float* rec, int32_t Hp, int32_t Wp, int32_t top, int32_t left, int32_t H, int32_t W,
+                      int32_t bitdepth, void* out, void* stream) {
+    CAI_CHECK_ARG(rec && out, "rgb_to_yuv420: null pointer");
+    vid_geom g;
+    int rc = vid_check("rgb_to_yuv420", out, out, out, H, W, bitdepth, Hp, Wp, top, left, &g);   // the planes are out's
+    if (rc != CAI_OK) return rc;
+    const int sample = bitdepth == 8 ? 1 : 2;
+    const int vec = (left % 2 == 0 && Wp % 2 == 0 && vid_aligned8(rec) ? 1 : 0) |
+                    ((reinterpret_cast<uintptr_t>(out) & (uintptr_t)(2 * sample - 1)) == 0 ? 2 : 0);
+    const float mv = (float)((1 << bitdepth) - 1);
+    const int grid = vid_grid((int64_t)(H / 2) * (W / 2));
+    hipStream_t st = as_stream(stream);
+#define CAI_YUV_LAUNCH(T, VEC)                                                                                     \
+    hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, VEC>), dim3(grid), dim3(256), 0, st, rec, g, mv, (T*)out)
+#define CAI_YUV_LAUNCH_T(T)                                                                                        \
+    switch (vec) {                                                                                                 \
+        case 3: CAI_YUV_LAUNCH(T, 3); break;                                                                       \
+        case 2: CAI_YUV_LAUNCH(T, 2); break;                                                                       \
+        case 1: CAI_YUV_LAUNCH(T, 1); break;                                                                       \
+        default: CAI_YUV_LAUNCH(T, 0); break;                                                                      \
+    }
+    if (bitdepth == 8) {
+        CAI_YUV_LAUNCH_T(uint8_t)
+    } else {
+        CAI_YUV_LAUNCH_T(uint16_t)
+    }
+#undef CAI_YUV_LAUNCH_T
+#undef CAI_YUV_LAUNCH
+    CAI_LAUNCH_CHECK("rgb_to_yuv420");
     return CAI_OK;
 }
 

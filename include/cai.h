@@ -857,6 +857,13 @@ int cai_yuv420_to_rgb(const void* y, const void* u, const void* v, int32_t H, in
 int cai_video_frame_sse(const void* y, const void* u, const void* v, int32_t H, int32_t W, int32_t bitdepth,
                         const float* org_q, const float* rec, int32_t Hp, int32_t Wp, int32_t top, int32_t left,
                         uint64_t* sums, float* rec_q, void* stream);
+/* rec fp32 [3][Hp][Wp] -> out: the H x W frame at (top, left) as H W 3 / 2 samples in file order, Y [H][W], then U
+ * [H/2][W/2], then V; uint8 at bitdepth 8, unsigned 16-bit words in host order above (out 2-byte aligned).  The
+ * levels are exactly those cai_video_frame_sse measures (one device function): rec clamped to [0, 1], BT.709 RGB ->
+ * YCbCr, Y = rint(clamp(y max_val, 0, max_val)) per pixel, U / V the same of the 2 x 2 mean.  One launch, plain
+ * stores.  CAI_EINVAL under the rules above, the planes being out's. */
+int cai_rgb_to_yuv420(const float* rec, int32_t Hp, int32_t Wp, int32_t top, int32_t left, int32_t H, int32_t W,
+                      int32_t bitdepth, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,9 @@ upload of the integer planes.  For scale: one encode_inter of ssf2020(1) at 1920
 Steps: frames8, frames10 (the A/B at 8 and 10 bits), model.  With --step all (the default) every step runs in a
 child process of its own under its own time limit, and the first failure ends the run.  A frame step prints, per
 path, the host-clock time of the whole per-frame path (upload .. metrics, ending in a device synchronise) as mean
-+- standard deviation over rounds that alternate between the paths, and the device time of the pieces between events.
++- standard deviation over rounds that alternate between the paths, and the device time of the pieces between events;
+then, timed the same way, the decoder's output path of utils/codec_rgbt: the reconstruction to an integer 4:2:0 frame
+on the host, frames.rgb_to_yuv420 + one copy against rgb_to_yuv420_torch + a copy per plane.
 usage: python tools/video_eval_bench.py [--step all|frames8|frames10|model] [--rounds 7] [--iters 20]"""
 import argparse
 import os
@@ -112,6 +114,23 @@ def frames_step(bitdepth, rounds, iters):
     for name, fn in pieces.items():
         t = [device(fn) for _ in range(rounds)]
         print(f"  {name:13s} (device events) {statistics.mean(t):8.1f} +- {statistics.stdev(t):6.1f} us")
+
+    # the decoder's output path (utils/codec_rgbt): reconstruction -> integer 4:2:0 frame on the host
+    outs = {"hip": lambda: frames.rgb_to_yuv420(x_rec, padding, bitdepth).buffer.cpu(),
+            "torch": lambda: [p.cpu() for p in frames.rgb_to_yuv420_torch(x_rec, padding, bitdepth)]}
+    differ = int((outs["hip"]() != torch.cat([p.reshape(-1) for p in outs["torch"]()])).sum())
+    for fn in outs.values():
+        for _ in range(3):
+            fn()
+    us = {p: [] for p in outs}
+    for _ in range(rounds):
+        for p, fn in outs.items():
+            us[p].append(wall(fn))
+    mh, mt = statistics.mean(us["hip"]), statistics.mean(us["torch"])
+    print(f"  decoded frame (host clock, reconstruction .. planes on the host; one launch + one copy against the torch "
+          f"body + three copies): hip {mh:8.1f} +- {statistics.stdev(us['hip']):6.1f} us   torch {mt:8.1f} +- "
+          f"{statistics.stdev(us['torch']):6.1f} us   torch / hip {mt / mh:.2f}x   levels that differ {differ} of "
+          f"{H * W * 3 // 2}")
 
 
 def model_step(rounds):
