@@ -150,6 +150,30 @@ def encode_streams(symbols: np.ndarray, indexes: np.ndarray, tables: Tables, nst
     return [out[out_off[s]:out_off[s] + nbytes[s]].tobytes() for s in range(nstreams)]
 
 
+class StreamDecoder:
+    """One persistent rANS decoder on one stream (cai_rans_decoder_*): successive decode() calls go on from the
+    state the previous one left, so a stream can be read in parts whose indexes depend on the parts before."""
+
+    def __init__(self, encoded: bytes):
+        self._h = lib.cai_rans_decoder_create()
+        if not self._h:
+            raise MemoryError("cai_rans_decoder_create failed")
+        data = np.frombuffer(bytes(encoded) or b"\0", dtype=np.uint8)
+        lib.cai_rans_decoder_set_stream(self._h, _ptr(data), len(encoded))     # copies the stream
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.cai_rans_decoder_destroy(h)
+
+    def decode(self, indexes: np.ndarray, tables: Tables) -> np.ndarray:
+        """The next indexes.size symbols -> int32 [indexes.size]."""
+        idx = i32(indexes).reshape(-1)
+        out = np.empty(idx.size, dtype=np.int32)
+        lib.cai_rans_decoder_decode_stream(self._h, _ptr(idx), idx.size, tables.ref(), _ptr(out))
+        return out
+
+
 def decode_streams(strings: Sequence[bytes], indexes: np.ndarray, tables: Tables) -> np.ndarray:
     """Inverse of encode_streams: -> int32 [nstreams, n]."""
     ns = len(strings)

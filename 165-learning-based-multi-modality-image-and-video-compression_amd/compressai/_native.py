@@ -245,6 +245,11 @@ SIGNATURES = {
     "cai_video_frame_sse": (_I, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32,
                                  _P, _P, _P]),
     "cai_rgb_to_yuv420": (_I, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "cai_parity_zero": (_I, [_I, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "cai_ckbd_quantize": (_I, [_P, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, _F, c_int32, c_int32, c_int32,
+                               c_int32, c_int32, _P, c_int32, _P, _P, _P]),
+    "cai_ckbd_indexes": (_I, [_P, c_int32, _P, c_int32, _F, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "cai_ckbd_dequantize": (_I, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),
 }
 
 

@@ -2206,6 +2206,114 @@ def ar_decode(pack: ArPack, strings: Sequence[bytes], params: torch.Tensor, with
     return out
 
 
+# ---------------------------------------------------------------------------
+# checkerboard context models (models/google.py, _ARCoding) -- csrc/ckbd.hip.  Parity of a position: (h + w) & 1,
+# 1 the anchors, 0 the non-anchors; the coder's order of an image is the anchors, then the non-anchors, each
+# group in raster order, channel-minor.
+# ---------------------------------------------------------------------------
+
+ANCHOR, NON_ANCHOR = 1, 0
+
+
+def ckbd_slot_range(H: int, W: int, parity: int) -> Tuple[int, int]:
+    """[lo, hi) of the slots of `parity` among an image's H W positions in the coder's order."""
+    n1 = H * W // 2
+    return (0, n1) if parity else (n1, H * W)
+
+
+def _parity_zero(x: torch.Tensor, parity: int, dt) -> torch.Tensor:
+    if parity not in (0, 1):
+        raise ValueError(f"parity must be 0 or 1, got {parity!r}")
+    xp, xld = to_pm(x, dt, 1)
+    out, old = _out_pm_like(x, dt)
+    B, C, H, W = x.shape
+    _ledger.run(lambda: lib.cai_parity_zero(dcode(dt), _p(xp), xld, _p(out), old, B, H, W, C, parity, _stream()),
+                "parity_zero", "parity_zero_kernel", 0, 1.5 * B * H * W * C * _es(dt), dt)
+    return out
+
+
+class ParityZeroFn(torch.autograd.Function):
+    """x with the positions of one parity ((h + w) & 1) set to exactly 0: the context features of a checkerboard
+    model at its anchors.  The backward is the same kernel on the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, parity: int):
+        _check_cuda(x)
+        if x.dim() != 4:
+            raise ValueError(f"parity_zero expects a [B, C, H, W] tensor, got {tuple(x.shape)}")
+        dt = compute_dtype()
+        ctx.cfg = (int(parity), dt)
+        return _parity_zero(x, int(parity), dt)
+
+    @staticmethod
+    def backward(ctx, g):
+        parity, dt = ctx.cfg
+        return _parity_zero(g, parity, dt), None
+
+
+def _ckbd_f32(t: torch.Tensor, shape=None) -> Tuple[torch.Tensor, int]:
+    _check_cuda(t)
+    if t.dim() != 4 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"checkerboard coding: expected a tensor of shape {shape}, got {tuple(t.shape)}")
+    return to_pm(t, torch.float32, 1)
+
+
+def _ckbd_ints(t: torch.Tensor, n: int, name: str) -> torch.Tensor:
+    _check_cuda(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"checkerboard coding: {name} must be a dense int32 tensor of {n} elements")
+    return t
+
+
+def _ckbd_out(y_hat: torch.Tensor, shape) -> int:
+    ld = pixel_major_ld(y_hat)
+    if y_hat.dtype != torch.float32 or tuple(y_hat.shape) != tuple(shape) or ld is None:
+        raise ValueError("checkerboard coding: y_hat must be a pixel-major fp32 tensor of y's shape")
+    return ld
+
+
+def ckbd_quantize(y, scales, means, scale_table, scale_bound: float, parity: int, y_hat, symbols, indexes):
+    """Encode pass of one parity (cai_ckbd_quantize): y, scales, means [B, C, H, W]; writes y_hat (pixel-major
+    fp32, in place) at the parity's positions and symbols / indexes (int32 [B, H W C]) at their slots."""
+    B, C, H, W = y.shape
+    yp, yld = _ckbd_f32(y)
+    sp, sld = _ckbd_f32(scales, y.shape)
+    mp, mld = _ckbd_f32(means, y.shape)
+    hld = _ckbd_out(y_hat, y.shape)
+    n = B * H * W * C
+    _ckbd_ints(symbols, n, "symbols"), _ckbd_ints(indexes, n, "indexes")
+    tab = scale_table.detach().float().contiguous()
+    _check_cuda(tab)
+    _ledger.run(lambda: lib.cai_ckbd_quantize(_p(yp), yld, _p(sp), sld, _p(mp), mld, _p(tab), tab.numel(),
+                                              float(scale_bound), B, H, W, C, int(parity), _p(y_hat), hld,
+                                              _p(symbols), _p(indexes), _stream()),
+                "ckbd_quantize", "ckbd_quantize_kernel", 0, 12.0 * n, torch.float32)
+
+
+def ckbd_indexes(scales, scale_table, scale_bound: float, parity: int, indexes):
+    """Decode pass of one parity, before the coder (cai_ckbd_indexes): the indexes at the parity's slots."""
+    B, C, H, W = scales.shape
+    sp, sld = _ckbd_f32(scales)
+    _ckbd_ints(indexes, B * H * W * C, "indexes")
+    tab = scale_table.detach().float().contiguous()
+    _check_cuda(tab)
+    _ledger.run(lambda: lib.cai_ckbd_indexes(_p(sp), sld, _p(tab), tab.numel(), float(scale_bound), B, H, W, C,
+                                             int(parity), _p(indexes), _stream()),
+                "ckbd_indexes", "ckbd_quantize_kernel", 0, 4.0 * B * H * W * C, torch.float32)
+
+
+def ckbd_dequantize(symbols, means, parity: int, y_hat):
+    """Decode pass of one parity, after the coder (cai_ckbd_dequantize): y_hat = symbols + means at the parity's
+    positions, the symbols read at their slots."""
+    B, C, H, W = means.shape
+    mp, mld = _ckbd_f32(means)
+    hld = _ckbd_out(y_hat, means.shape)
+    _ckbd_ints(symbols, B * H * W * C, "symbols")
+    _ledger.run(lambda: lib.cai_ckbd_dequantize(_p(symbols), _p(mp), mld, B, H, W, C, int(parity), _p(y_hat), hld,
+                                                _stream()),
+                "ckbd_dequantize", "ckbd_dequantize_kernel", 0, 6.0 * B * H * W * C, torch.float32)
+
+
 def _like_logical(d: torch.Tensor, buf: torch.Tensor, shape) -> torch.Tensor:
     """d has buf's memory layout; return it as a tensor of the likelihood's logical shape."""
     if tuple(buf.shape) == tuple(shape):

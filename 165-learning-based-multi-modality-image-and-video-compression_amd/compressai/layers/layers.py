@@ -2,7 +2,9 @@
 
 MaskedConv2d follows layers.py:52-78: the weight is masked in place before
 every call (so gradients reach masked taps exactly as in the reference), then
-the conv runs on the HIP implicit-GEMM kernel.
+the conv runs on the HIP implicit-GEMM kernel.  mask_type="checkerboard"
+(CheckerboardMaskedConv2d) is the 12-tap mask of the checkerboard context
+models; its masked taps take a gradient of exactly 0.
 
 The residual / attention blocks of the cheng2020 models (layers.py:97-244)
 keep the reference's module tree (so state_dict keys match: ``conv1``,
@@ -21,12 +23,12 @@ import torch
 import torch.nn as nn
 
 from .._native import ACT_LEAKY, ACT_NONE, ACT_RELU, MASK_LEAKY, MASK_POS
-from .._ops import (AddActFn, AttentionBlockFn, GateFn, QReluFn, ResidualBlockFn, ResidualChainFn, _ab_side, fan_out,
+from .._ops import (AddActFn, AttentionBlockFn, ConvFn, GateFn, QReluFn, ResidualBlockFn, ResidualChainFn, _ab_side, fan_out,
                     residual_fusable)
 from .conv import Conv2d, ConvTranspose2d, PixelShuffle, Sequential
 from .gdn import GDN
 
-__all__ = ["MaskedConv2d", "conv1x1", "conv3x3", "subpel_conv3x3", "PixelShuffle", "ResidualBlockWithStride",
+__all__ = ["MaskedConv2d", "CheckerboardMaskedConv2d", "conv1x1", "conv3x3", "subpel_conv3x3", "PixelShuffle", "ResidualBlockWithStride",
            "ResidualBlockUpsample", "ResidualBlock", "AttentionBlock", "QReLU"]
 
 _SLOPE = 0.01   # nn.LeakyReLU() default negative_slope
@@ -35,16 +37,48 @@ _SLOPE = 0.01   # nn.LeakyReLU() default negative_slope
 class MaskedConv2d(Conv2d):
     def __init__(self, *args: Any, mask_type: str = "A", **kwargs: Any):
         super().__init__(*args, **kwargs)
-        if mask_type not in ("A", "B"):
+        if mask_type not in ("A", "B", "checkerboard"):
             raise ValueError(f'Invalid "mask_type" value "{mask_type}"')
         self.register_buffer("mask", torch.ones_like(self.weight.data))
+        self._mask_grad = mask_type == "checkerboard"
         _, _, h, w = self.mask.size()
+        if mask_type == "checkerboard":
+            # the taps at odd (i + j): from a position of one parity of (h + w), exactly the other parity's
+            # positions (He et al., CVPR 2021); 12 taps of a 5x5 kernel, the centre is 0
+            i, j = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+            self.mask[:, :, (i + j) % 2 == 0] = 0
+            return
         self.mask[:, :, h // 2, w // 2 + (mask_type == "B"):] = 0
         self.mask[:, :, h // 2 + 1:] = 0
 
     def run(self, x, **kw):
         self.weight.data *= self.mask
+        if self._mask_grad and torch.is_grad_enabled() and self.weight.requires_grad:
+            return ConvFn.apply(x, _MaskedWeightFn.apply(self.weight, self.mask), self.bias, self._spec(**kw))
         return super().run(x, **kw)
+
+
+class _MaskedWeightFn(torch.autograd.Function):
+    """weight * mask as its own tensor, its gradient masked too: the checkerboard conv's masked taps get a gradient
+    of exactly 0 (through `weight.data *= mask` alone they get the unmasked conv's, as the raster masks do in the
+    reference, and an optimizer's moments then move taps the next forward zeroes again)."""
+
+    @staticmethod
+    def forward(ctx, weight, mask):
+        ctx.save_for_backward(mask)
+        return weight * mask
+
+    @staticmethod
+    def backward(ctx, g):
+        (mask,) = ctx.saved_tensors
+        return g * mask, None
+
+
+class CheckerboardMaskedConv2d(MaskedConv2d):
+    """MaskedConv2d(..., mask_type="checkerboard") under upstream CompressAI's name."""
+
+    def __init__(self, *args: Any, **kwargs: Any):
+        super().__init__(*args, mask_type="checkerboard", **kwargs)
 
 
 def conv3x3(in_ch: int, out_ch: int, stride: int = 1) -> nn.Module:

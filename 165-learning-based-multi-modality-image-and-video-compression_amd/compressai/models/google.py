@@ -28,11 +28,18 @@ encoder and decoder reproduce each other's scales exactly), symbols from the
 quantize kernel, rANS strings from libcai_coder.so.  The autoregressive
 models' serial per-latent-pixel loop runs the masked 5x5 context conv and
 the 1x1 entropy-parameter stack on the same kernels, one pixel at a time.
+
+The context models also take context="checkerboard" (He et al., CVPR 2021; no
+counterpart in the reference): a 12-tap checkerboard mask, the context features
+zeroed at the anchors (odd h + w), and compress / decompress in two dense
+passes over the whole latent instead of the scan (_ARCoding._ckbd_*,
+csrc/ckbd.hip).
 """
 import math
 import os
 import warnings
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -48,7 +55,7 @@ from ..layers.conv import Conv2d
 from .utils import conv, deconv, update_registered_buffers
 
 __all__ = ["CompressionModel", "FactorizedPrior", "ScaleHyperprior", "MeanScaleHyperprior",
-           "JointAutoregressiveHierarchicalPriors", "get_scale_table", "SCALES_MIN", "SCALES_MAX", "SCALES_LEVELS"]
+           "JointAutoregressiveHierarchicalPriors", "context_of", "get_scale_table", "SCALES_MIN", "SCALES_MAX", "SCALES_LEVELS"]
 
 SCALES_MIN = 0.11
 SCALES_MAX = 256
@@ -461,6 +468,21 @@ class MeanScaleHyperprior(ScaleHyperprior):
         return {"x_hat": x_hat}
 
 
+def context_of(state_dict, default="raster"):
+    """The context ("raster" / "checkerboard") a context model's checkpoint was trained with, read from its
+    context_prediction.mask; `default` when the checkpoint has no such buffer."""
+    mask = state_dict.get("context_prediction.mask")
+    if mask is None:
+        return default
+    m = mask.detach().reshape(-1, *mask.shape[-2:])[0].cpu() != 0
+    h, w = m.shape
+    for context, mask_type in (("raster", "A"), ("checkerboard", "checkerboard")):
+        if torch.equal(MaskedConv2d(1, 1, (h, w), mask_type=mask_type).mask[0, 0] != 0, m):
+            return context
+    raise ValueError("context_prediction.mask of the checkpoint is neither the raster (type A) nor the checkerboard "
+                     "mask")
+
+
 class _ARCoding:
     """Serial autoregressive entropy coding of the context models (google.py:565-608, 654-692), shared by
     JointAutoregressiveHierarchicalPriors and the multi-modal Guided / Master codecs (master.py:993-1147,
@@ -470,13 +492,52 @@ class _ARCoding:
     _AR_SPEC = None
     AR_BACKENDS = ("serial", "fused")
     _ar_backend = "serial"
+    CONTEXTS = ("raster", "checkerboard")
+    _context = "raster"
+
+    @property
+    def context(self) -> str:
+        """"raster" (default): the reference's autoregressive context model, coded pixel by pixel in raster order
+        (ar_backend chooses how).  "checkerboard" (He et al., CVPR 2021): the positions with odd h + w, the
+        anchors, are coded from the hyperprior alone, the others from the hyperprior and a masked conv over the
+        decoded anchors: two dense passes on the GPU.  A property of the trained model, set by the constructor's
+        `context` argument; ar_backend is not consulted for a checkerboard model."""
+        return self._context
+
+    def _make_context_prediction(self, M, context):
+        """The context conv of `context` (same module name, state_dict keys and shapes for both)."""
+        if context not in self.CONTEXTS:
+            raise ValueError(f"context must be one of {self.CONTEXTS}, got {context!r}")
+        self._context = context
+        return MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1,
+                            mask_type="checkerboard" if context == "checkerboard" else "A")
+
+    def _ctx_params(self, y_hat):
+        """context_prediction(y_hat); for a checkerboard model set to exactly 0 at the anchors, bias included."""
+        ctx = self.context_prediction(y_hat)
+        if self._context == "checkerboard":
+            from .._ops import ANCHOR, ParityZeroFn
+
+            ctx = ParityZeroFn.apply(ctx, ANCHOR)
+        return ctx
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """A checkpoint's context_prediction.mask is a buffer and would replace the model's silently: a
+        checkpoint of the other context is refused."""
+        theirs = context_of(state_dict, default=None)
+        if theirs is not None and theirs != self._context:
+            raise ValueError(f'the checkpoint was trained with context="{theirs}" (its context_prediction.mask) and '
+                             f'cannot be loaded into a model built with context="{self._context}"; build the model '
+                             f'with context="{theirs}" (from_state_dict does)')
+        return super().load_state_dict(state_dict, strict=strict)
 
     @property
     def ar_backend(self) -> str:
         """"serial" (default): the reference's per-pixel loop on the conv kernels, coded on the host.
         "fused": the whole scan of the batch in one launch (csrc/ar_coder.hip), decoding on the device.
         The two sum the entropy parameters in different orders, so a stream must be read by the backend that
-        wrote it."""
+        wrote it.  Not consulted for a checkerboard model (see `context`), which is coded in two dense passes
+        whatever this says."""
         return self._ar_backend
 
     @ar_backend.setter
@@ -532,6 +593,8 @@ class _ARCoding:
 
     @staticmethod
     def _warn_gpu(model):
+        if getattr(model, "context", "raster") == "checkerboard":   # two dense passes on the GPU: nothing to warn of
+            return
         if getattr(model, "ar_backend", "serial") == "fused":
             if next(model.parameters()).device.type != "cuda":
                 raise ValueError('ar_backend="fused" runs on the GPU only and the model is on a CPU device; there '
@@ -543,6 +606,8 @@ class _ARCoding:
 
     def _ar_encode_all(self, y, params):
         """y_strings of a batch (google.py:542-561)."""
+        if self._context == "checkerboard":
+            return self._ckbd_encode(y, params)["strings"]
         if self.ar_backend == "fused":
             return self._ar_encode_fused(y, params)["strings"]
         cp = self.context_prediction
@@ -556,6 +621,8 @@ class _ARCoding:
 
     def _ar_decode_all(self, y_strings, params):
         """y_hat of a batch (google.py:622-650)."""
+        if self._context == "checkerboard":
+            return self._ckbd_decode(y_strings, params)
         if self.ar_backend == "fused":
             from .. import _ops
 
@@ -570,6 +637,98 @@ class _ARCoding:
         for i, y_string in enumerate(y_strings):
             self._decompress_ar(y_string, y_hat[i:i + 1], params[i:i + 1], y_height, y_width, kernel_size, padding)
         return F.pad(y_hat, (-padding, -padding, -padding, -padding))
+
+    # ---- checkerboard: two dense passes ---------------------------------------------------------------------
+
+    def _ckbd_pass(self, params, y_hat, parity):
+        """(scales, means) of one pass over the whole map, shared by the encoder and the decoder so that both
+        launch the same kernels on the same shapes.  Anchors: entropy_parameters(cat(params, 0)); non-anchors:
+        the masked conv over y_hat (the decoded anchors; zeros elsewhere), zeroed at the anchors, and the same
+        stack."""
+        from .._ops import ANCHOR
+
+        if parity == ANCHOR:
+            B, _, H, W = params.shape
+            ctx = torch.zeros((B, H, W, self.context_prediction.out_channels), dtype=torch.float32,
+                              device=params.device).permute(0, 3, 1, 2)
+        else:
+            ctx = self._ctx_params(y_hat)
+        return ChunkFn.apply(self.entropy_parameters(CatFn.apply(params, ctx)))
+
+    def _ckbd_begin(self, params):
+        gc = self.gaussian_conditional
+        if not params.is_cuda or not self.context_prediction.weight.is_cuda:
+            raise ValueError("checkerboard coding runs on the GPU only (model and input on a CPU device); there is "
+                             "no CPU fallback, an encoder and a decoder on different devices would not agree")
+        gc._check_cdf_size()
+        gc._check_cdf_length()
+        gc._check_offsets_size()
+        B, _, H, W = params.shape
+        M = self.context_prediction.in_channels
+        # y_hat starts as zeros: a masked-out weight times an uninitialised NaN is NaN
+        y_hat = torch.zeros((B, H, W, M), dtype=torch.float32, device=params.device).permute(0, 3, 1, 2)
+        return gc, y_hat, (B, M, H, W)
+
+    def _ckbd_encode(self, y, params, with_params=False):
+        """Pass A codes the anchors, pass B the non-anchors; one stream per image, the anchors' symbols first:
+        {"strings", "y_hat", "symbols", "indexes"} (+ "scales", "means" [B, M, H, W], each position's from the
+        pass that coded it, with with_params).  fp32, autocast off."""
+        from .. import _coder, _ops
+
+        with torch.autocast("cuda", enabled=False):
+            params = params.float()
+            gc, y_hat, (B, M, H, W) = self._ckbd_begin(params)
+            y = y.float()
+            if tuple(y.shape) != (B, M, H, W):
+                raise ValueError(f"checkerboard coding: y {tuple(y.shape)} / params {tuple(params.shape)} do not "
+                                 "match the model")
+            symbols = torch.empty(B, H * W * M, dtype=torch.int32, device=y.device)
+            indexes = torch.empty_like(symbols)
+            used = {}
+            for parity in (_ops.ANCHOR, _ops.NON_ANCHOR):
+                lo, hi = _ops.ckbd_slot_range(H, W, parity)
+                if hi == lo:        # a 1 x 1 latent has no anchors
+                    continue
+                scales, means = self._ckbd_pass(params, y_hat, parity)
+                _ops.ckbd_quantize(y, scales, means, gc.scale_table, gc._scale_bound_value, parity, y_hat, symbols,
+                                   indexes)
+                if with_params:
+                    used[parity] = (scales, means)
+        out = {"y_hat": y_hat, "symbols": symbols, "indexes": indexes}
+        if with_params:
+            h = torch.arange(H, device=y.device).view(H, 1)
+            w = torch.arange(W, device=y.device).view(1, W)
+            anchor = ((h + w) % 2 == 1).expand(B, M, H, W)
+            a, n = used.get(_ops.ANCHOR, used[_ops.NON_ANCHOR]), used[_ops.NON_ANCHOR]
+            out["scales"], out["means"] = torch.where(anchor, a[0], n[0]), torch.where(anchor, a[1], n[1])
+        out["strings"] = _coder.encode_streams(symbols.cpu().numpy(), indexes.cpu().numpy(), gc._tables(), B)
+        return out
+
+    def _ckbd_decode(self, y_strings, params):
+        """y_hat of a batch: one persistent host decoder per image reads the anchors' symbols after pass A and
+        the others' after pass B, from the state the anchors left."""
+        from .. import _coder, _ops
+
+        with torch.autocast("cuda", enabled=False):
+            params = params.float()
+            gc, y_hat, (B, M, H, W) = self._ckbd_begin(params)
+            if len(y_strings) != B:
+                raise ValueError("checkerboard coding: one string per batch element expected")
+            tables = gc._tables()
+            decoders = [_coder.StreamDecoder(s) for s in y_strings]
+            symbols = torch.zeros(B, H * W * M, dtype=torch.int32, device=params.device)
+            indexes = torch.zeros_like(symbols)
+            for parity in (_ops.ANCHOR, _ops.NON_ANCHOR):
+                lo, hi = _ops.ckbd_slot_range(H, W, parity)
+                if hi == lo:
+                    continue
+                scales, means = self._ckbd_pass(params, y_hat, parity)
+                _ops.ckbd_indexes(scales, gc.scale_table, gc._scale_bound_value, parity, indexes)
+                idx = indexes[:, lo * M:hi * M].cpu().numpy()
+                sym = np.stack([d.decode(idx[b], tables) for b, d in enumerate(decoders)])
+                symbols[:, lo * M:hi * M] = torch.from_numpy(sym).to(params.device)
+                _ops.ckbd_dequantize(symbols, means, parity, y_hat)
+        return y_hat
 
     def _ar_encode_fused(self, y, params, with_params=False):
         """One kernel call for the batch, then the host coder on its symbols: {"strings", "y_hat", "symbols",
@@ -624,13 +783,21 @@ class JointAutoregressiveHierarchicalPriors(_ARCoding, MeanScaleHyperprior):
     # gradient buckets (dp_phases): g_s (pieces: dp_gs_cuts), the context model + entropy parameters (their
     # gradients are final once the backward reaches h_s's output, cut "params"), the hyper path, then g_a
     dp_head_splits = ((("entropy_parameters.", "context_prediction."), "params"),)
-    def __init__(self, N=192, M=192, channel=3, **kwargs):
+    def __init__(self, N=192, M=192, channel=3, context="raster", **kwargs):
         super().__init__(N=N, M=M, channel=channel, **kwargs)
         self.entropy_parameters = Sequential(
             Conv2d(M * 12 // 3, M * 10 // 3, 1), nn.LeakyReLU(inplace=True),
             Conv2d(M * 10 // 3, M * 8 // 3, 1), nn.LeakyReLU(inplace=True),
             Conv2d(M * 8 // 3, M * 6 // 3, 1))
-        self.context_prediction = MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+        self.context_prediction = self._make_context_prediction(M, context)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, channel=3):
+        """The context is the checkpoint's (context_of)."""
+        net = cls(state_dict["g_a.0.weight"].size(0), state_dict["g_a.6.weight"].size(0), channel=channel,
+                  context=context_of(state_dict))
+        net.load_state_dict(state_dict)
+        return net
 
     def forward(self, x):
         y = self._dp_cut(self.g_a(x))
@@ -643,7 +810,7 @@ class JointAutoregressiveHierarchicalPriors(_ARCoding, MeanScaleHyperprior):
             params = self._dp_mark("params", self.h_s(z_hat))
             y_hat = self.gaussian_conditional.quantize(y_q, "noise" if self.training else "dequantize")
             y_ctx, y_gs = fan_out(y_hat, absorb=False)
-            ctx_params = self.context_prediction(y_ctx)
+            ctx_params = self._ctx_params(y_ctx)
             gaussian_params = self.entropy_parameters(CatFn.apply(params, ctx_params))
             scales_hat, means_hat = ChunkFn.apply(gaussian_params)
             _, y_likelihoods = self.gaussian_conditional(y_gc, scales_hat, means=means_hat)
@@ -668,7 +835,7 @@ class JointAutoregressiveHierarchicalPriors(_ARCoding, MeanScaleHyperprior):
         x_hat = self.g_s(self._dp_mark("gs_in", y_gs))
         with torch.cuda.stream(side):
             side.wait_event(ready)
-            ctx_params = self.context_prediction(y_ctx)
+            ctx_params = self._ctx_params(y_ctx)
             gaussian_params = self.entropy_parameters(CatFn.apply(params, ctx_params))
             scales_hat, means_hat = ChunkFn.apply(gaussian_params)
             _, y_likelihoods = self.gaussian_conditional(y_gc, scales_hat, means=means_hat, noise=noise2)

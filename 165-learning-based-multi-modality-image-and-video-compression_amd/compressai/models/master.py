@@ -346,8 +346,9 @@ class Master_decoder(nn.Module):
 # codecs
 # ---------------------------------------------------------------------------
 
-def _jahp_tail(model, N, M):
-    """Hyperprior + context entropy path shared by Master / Guided (master.py:240-270, 1231-1265)."""
+def _jahp_tail(model, N, M, context="raster"):
+    """Hyperprior + context entropy path shared by Master / Guided (master.py:240-270, 1231-1265); `context`:
+    _ARCoding.context."""
     model.h_a = Sequential(conv(M, N, stride=1, kernel_size=3), nn.LeakyReLU(inplace=True),
                            conv(N, N, stride=2, kernel_size=5), nn.LeakyReLU(inplace=True),
                            conv(N, N, stride=2, kernel_size=5))
@@ -358,7 +359,7 @@ def _jahp_tail(model, N, M):
         Conv2d(M * 12 // 3, M * 10 // 3, 1), nn.LeakyReLU(inplace=True),
         Conv2d(M * 10 // 3, M * 8 // 3, 1), nn.LeakyReLU(inplace=True),
         Conv2d(M * 8 // 3, M * 6 // 3, 1))
-    model.context_prediction = MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+    model.context_prediction = model._make_context_prediction(M, context)
     model.gaussian_conditional = GaussianConditional(None)
     model.N, model.M = int(N), int(M)
 
@@ -369,7 +370,7 @@ def _entropy(model, y):
     params = model._dp_mark("params", model.h_s(z_hat))
     yq = model._dp_mark("yq", y)        # y as quantize / the GaussianConditional read it (Master's dp_phases)
     y_hat = model.gaussian_conditional.quantize(yq, "noise" if model.training else "dequantize")
-    ctx = model.context_prediction(y_hat)
+    ctx = model._ctx_params(y_hat)
     scales_hat, means_hat = model.entropy_parameters(CatFn.apply(params, ctx)).chunk(2, 1)
     _, y_lik = model.gaussian_conditional(yq, scales_hat, means=means_hat)
     return y_hat, y_lik, z_lik
@@ -384,7 +385,7 @@ class Master_compresser(_ARCoding, MeanScaleHyperprior):
     dp_tail = ("fencoder1.", "fencoder2.", "ch_aligner.")
     dp_tail_cuts = ()     # one tail bucket (10.6 MB against a ~57 ms pair step)
 
-    def __init__(self, width=256, height=256, channel=3, N=192, M=192):
+    def __init__(self, width=256, height=256, channel=3, N=192, M=192, context="raster"):
         super().__init__(M, M)
         master_chl, guided_chl, master_stride, guided_stride = 3, 1, 2, 1
         if channel == 1:
@@ -393,7 +394,7 @@ class Master_compresser(_ARCoding, MeanScaleHyperprior):
         self.fencoder2 = Feature_encoder(in_channel=guided_chl, out_channel=64, stride=guided_stride)
         self.ch_aligner = Channel_aligner()
         self.g_a = Sequential(conv(64 * 2, N), GDN(N), conv(N, N), GDN(N), conv(N, N), GDN(N), conv(N, M))
-        _jahp_tail(self, N, M)
+        _jahp_tail(self, N, M, context)
         self.decoder = Master_decoder(N=192, M=192, channel=64 * 2, width=width, height=height, first_stride=2,
                                       master_chl=master_chl)
         self.fdecoder = Feature_decoder(in_channel=64 * 3, out_channel=master_chl, stride=master_stride)
@@ -496,12 +497,12 @@ class Decoder1(nn.Module):
 class Guided_compresser(_ARCoding, MeanScaleHyperprior):
     """master.py:1215-1295: net(x) -> {"x_hat", "likelihoods", "hidden": {ga1..3, gs1..3}}."""
 
-    def __init__(self, N=192, M=192, channel=1, first_stride=2, **kwargs):
+    def __init__(self, N=192, M=192, channel=1, first_stride=2, context="raster", **kwargs):
         super().__init__(N=N, M=M, **kwargs)
         self.first_stride = first_stride
         self.enc1 = Encoder1(N, M, channel, first_stride)
         self.dec1 = Decoder1(N, M, channel, first_stride)
-        _jahp_tail(self, N, M)
+        _jahp_tail(self, N, M, context)
 
     @property
     def downsampling_factor(self) -> int:

@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ..layers import (AttentionBlock, ResidualBlock, ResidualBlockUpsample, ResidualBlockWithStride, Sequential,
                       conv3x3, subpel_conv3x3)
-from .google import JointAutoregressiveHierarchicalPriors
+from .google import JointAutoregressiveHierarchicalPriors, context_of
 
 __all__ = ["Cheng2020Anchor", "Cheng2020Attention"]
 
@@ -47,7 +47,7 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
     def from_state_dict(cls, state_dict, channel=3):
         """waseda.py:115-121."""
         N = state_dict["g_a.0.conv1.weight"].size(0)
-        net = cls(N, channel)
+        net = cls(N, channel, context=context_of(state_dict))
         net.load_state_dict(state_dict)
         return net
 

@@ -185,13 +185,16 @@ def _state_dict_from(path: str) -> Dict[str, torch.Tensor]:
 def load_checkpoint(arch: str, checkpoint_path: str, channel: int = 3, **kwargs) -> torch.nn.Module:
     """__main__t.py:220-222, plus the fork's multi-modal classes."""
     from compressai.models import Guided_compresser, Master_compresser
+    from compressai.models.google import context_of
 
     sd = _state_dict_from(checkpoint_path)
+    # the context models take their context (raster / checkerboard) from the checkpoint's mask
     if arch in ("Guided_compresser", "guided"):
-        model = Guided_compresser(channel=channel)
+        model = Guided_compresser(channel=channel, context=context_of(sd))
         model.load_state_dict(sd)
     elif arch in ("Master_compresser", "master"):
-        model = Master_compresser(width=kwargs.get("width", 256), height=kwargs.get("height", 256), channel=channel)
+        model = Master_compresser(width=kwargs.get("width", 256), height=kwargs.get("height", 256), channel=channel,
+                                  context=context_of(sd))
         model.load_state_dict(sd)
     elif arch in architectures:
         model = architectures[arch].from_state_dict(sd, channel=channel)

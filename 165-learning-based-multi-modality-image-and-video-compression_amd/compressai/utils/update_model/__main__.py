@@ -27,6 +27,7 @@ import torch
 
 from compressai.models import (FactorizedPrior, Guided_compresser, JointAutoregressiveHierarchicalPriors,
                                Master_compresser, MeanScaleHyperprior, ScaleHyperprior)
+from compressai.models.google import context_of
 from compressai.zoo import load_state_dict
 from compressai.zoo.image import model_architectures as zoo_models
 
@@ -86,11 +87,11 @@ def build(architecture: str, state_dict, channel: int):
     if architecture in _NOT_BUILT:
         raise ValueError(f'architecture "{architecture}" is not part of this build')
     if architecture == "Guided_compresser":
-        net = Guided_compresser(channel=channel)
+        net = Guided_compresser(channel=channel, context=context_of(state_dict))
         net.load_state_dict(state_dict)
         return net
     if architecture == "Master_compresser":
-        net = Master_compresser(width=512, height=640, channel=channel)
+        net = Master_compresser(width=512, height=640, channel=channel, context=context_of(state_dict))
         net.load_state_dict(state_dict)
         return net
     if architecture not in models:

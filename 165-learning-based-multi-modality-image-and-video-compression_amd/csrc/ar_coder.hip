@@ -124,10 +124,7 @@ __device__ __forceinline__ void ar_pixel_params(const ar_kargs& k, float* sm, in
 
 // GaussianConditional.build_indexes: clamp at the bound, then L-1 - #{s in table[:-1] : scale <= s}
 __device__ __forceinline__ int ar_index(float scale, float bound, const float* tab, int L) {
-    scale = scale < bound ? bound : scale;
-    int idx = L - 1;
-    for (int j = 0; j < L - 1; ++j) idx -= scale <= tab[j] ? 1 : 0;
-    return idx;
+    return gc_scale_index(scale, bound, tab, L);
 }
 
 // The slot search of rans_decode.hpp's decode_symbol by a whole wave (every lane calls it with the same

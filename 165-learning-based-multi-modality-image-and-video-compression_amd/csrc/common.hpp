@@ -67,6 +67,21 @@ __device__ __forceinline__ void st_any(void* p, int dtype, int64_t i, float v) {
 static inline int dtype_size(int dtype) { return dtype == CAI_BF16 ? 2 : 4; }
 
 // ---------------------------------------------------------------------------
+// the discrete steps of the GaussianConditional's coding side, one definition for every kernel that takes them
+// (quantize_kernel, the fused autoregressive scan, the checkerboard passes): encoder and decoder must agree on
+// the integers
+// ---------------------------------------------------------------------------
+// GaussianConditional.build_indexes: clamp at the bound, then L-1 - #{s in table[:-1] : scale <= s}
+__device__ __forceinline__ int gc_scale_index(float scale, float bound, const float* tab, int L) {
+    scale = scale < bound ? bound : scale;
+    int idx = L - 1;
+    for (int j = 0; j < L - 1; ++j) idx -= scale <= tab[j] ? 1 : 0;
+    return idx;
+}
+// EntropyModel.quantize's rounding of the residual (torch.round = half-to-even)
+__device__ __forceinline__ float gc_round(float v, float mu) { return rintf(v - mu); }
+
+// ---------------------------------------------------------------------------
 // wave / block reductions (wave = 64 lanes)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

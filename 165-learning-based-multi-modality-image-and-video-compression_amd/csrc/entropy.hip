@@ -130,7 +130,7 @@ __global__ void quantize_kernel(int mode, int64_t n, int C, const void* __restri
         }
         float mu = 0.f;
         if (means) mu = means_pc ? means[c] : means[p * mld + c];
-        float r = rintf(means ? v - mu : v);
+        float r = means ? gc_round(v, mu) : rintf(v);
         if (mode == CAI_Q_SYMBOLS) {
             reinterpret_cast<int32_t*>(out)[p * old + c] = (int32_t)r;
         } else {

@@ -865,6 +865,35 @@ int cai_video_frame_sse(const void* y, const void* u, const void* v, int32_t H, 
 int cai_rgb_to_yuv420(const float* rec, int32_t Hp, int32_t Wp, int32_t top, int32_t left, int32_t H, int32_t W,
                       int32_t bitdepth, void* out, void* stream);
 
+/* =======================================================================
+ * Checkerboard context models (csrc/ckbd.hip): the parity kernels around the two dense passes.  Tensors are
+ * pixel-major [B][H][W] pixels of C channels with a channel stride ld >= C (scales and means may be the channel
+ * halves of one buffer, ld = 2 C).  The parity of a position is (h + w) & 1: 1 the anchors, 0 the non-anchors;
+ * an H x W map has n1 = floor(H W / 2) anchors and n0 = H W - n1 non-anchors.  In the coder's order an image's
+ * H W C integers are the anchors' (slots 0 .. n1 - 1), then the non-anchors' (slots n1 .. H W - 1), each group in
+ * raster order with the C channels of a position adjacent: symbols / indexes are dense int32 [B][H W][C].
+ * 16-byte accesses along the channels when C, every ld and every pointer allow them, scalar accesses otherwise.
+ * CAI_EINVAL before any launch for null pointers, B, H, W or C below 1, a ld below C, a parity other than 0 / 1,
+ * B H W C at or above 2^31.
+ * ======================================================================= */
+/* out = x with the positions of `parity` set to 0 (dtype CAI_F32 / CAI_BF16; out may not alias x). */
+int cai_parity_zero(int dtype, const void* x, int32_t x_ld, void* out, int32_t out_ld, int32_t B, int32_t H,
+                    int32_t W, int32_t C, int32_t parity, void* stream);
+/* Encode pass over the positions of `parity`: indexes = GaussianConditional.build_indexes(scales) (the fused
+ * autoregressive coder's device function), symbols = (int)rint(y - means) (cai_quantize's), both at the positions'
+ * slots, and y_hat = symbols + means at the positions.  Nothing else is written.  y NULL: indexes only (y_hat and
+ * symbols are not touched and may be NULL). */
+int cai_ckbd_quantize(const float* y, int32_t y_ld, const float* scales, int32_t s_ld, const float* means,
+                      int32_t m_ld, const float* scale_table, int32_t n_scales, float scale_bound, int32_t B,
+                      int32_t H, int32_t W, int32_t C, int32_t parity, float* y_hat, int32_t yh_ld, int32_t* symbols,
+                      int32_t* indexes, void* stream);
+/* Decode pass, before the coder: the indexes of `parity` at their slots (cai_ckbd_quantize with a null y). */
+int cai_ckbd_indexes(const float* scales, int32_t s_ld, const float* scale_table, int32_t n_scales, float scale_bound,
+                     int32_t B, int32_t H, int32_t W, int32_t C, int32_t parity, int32_t* indexes, void* stream);
+/* Decode pass, after the coder: y_hat = symbols (read at the slots of `parity`) + means at the positions. */
+int cai_ckbd_dequantize(const int32_t* symbols, const float* means, int32_t m_ld, int32_t B, int32_t H, int32_t W,
+                        int32_t C, int32_t parity, float* y_hat, int32_t yh_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
