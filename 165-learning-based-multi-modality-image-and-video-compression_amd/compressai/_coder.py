@@ -134,8 +134,10 @@ def pmf_to_quantized_cdf_rows(pmf: np.ndarray, lengths: np.ndarray, precision: i
     return out
 
 
-def encode_streams(symbols: np.ndarray, indexes: np.ndarray, tables: Tables, nstreams: int) -> list:
-    """Equal-length streams (one per image): symbols/indexes [nstreams, n] -> list of bytes."""
+def encode_streams(symbols: np.ndarray, indexes: np.ndarray, tables: Tables, nstreams: int,
+                   threads: Optional[int] = None) -> list:
+    """Equal-length streams (one per image): symbols/indexes [nstreams, n] -> list of bytes.  threads: host threads
+    of this call (default: default_threads()); callers that already run on a pool pass their share."""
     sym = i32(symbols).reshape(nstreams, -1)
     idx = i32(indexes).reshape(nstreams, -1)
     n = sym.shape[1]
@@ -146,7 +148,7 @@ def encode_streams(symbols: np.ndarray, indexes: np.ndarray, tables: Tables, nst
     nbytes = np.zeros(nstreams, dtype=np.int64)
     if nstreams:
         lib.cai_rans_encode_batch(nstreams, _ptr(sym), _ptr(idx), _ptr(sym_off), tables.ref(), _ptr(out),
-                                  _ptr(out_off), _ptr(nbytes), default_threads())
+                                  _ptr(out_off), _ptr(nbytes), default_threads() if threads is None else int(threads))
     return [out[out_off[s]:out_off[s] + nbytes[s]].tobytes() for s in range(nstreams)]
 
 
@@ -178,14 +180,24 @@ def decode_streams(strings: Sequence[bytes], indexes: np.ndarray, tables: Tables
     """Inverse of encode_streams: -> int32 [nstreams, n]."""
     ns = len(strings)
     idx = i32(indexes).reshape(ns, -1)
+    return decode_streams_into(strings, idx, tables, np.empty(idx.shape, dtype=np.int32))
+
+
+def decode_streams_into(strings: Sequence[bytes], indexes: np.ndarray, tables: Tables, out: np.ndarray,
+                        threads: Optional[int] = None) -> np.ndarray:
+    """decode_streams into a caller's dense int32 array of indexes' size (a pinned staging buffer, say)."""
+    ns = len(strings)
+    idx = i32(indexes).reshape(ns, -1)
     n = idx.shape[1]
+    if out.dtype != np.int32 or not out.flags.c_contiguous or out.size != idx.size:
+        raise ValueError("decode_streams_into: out must be a dense int32 array of the indexes' size")
+    out = out.reshape(ns, n)
     blob = np.frombuffer(b"".join(bytes(s) for s in strings) or b"\0", dtype=np.uint8)
     lens = np.array([len(s) for s in strings], dtype=np.int64)
     data_off = np.zeros(ns + 1, dtype=np.int64)
     data_off[1:] = np.cumsum(lens)
     sym_off = np.arange(ns + 1, dtype=np.int64) * n
-    out = np.empty((ns, n), dtype=np.int32)
     if ns:
         lib.cai_rans_decode_batch(ns, _ptr(blob), _ptr(data_off), _ptr(lens), _ptr(idx), _ptr(sym_off), tables.ref(),
-                                  _ptr(out), default_threads())
+                                  _ptr(out), default_threads() if threads is None else int(threads))
     return out

@@ -250,6 +250,10 @@ SIGNATURES = {
                                c_int32, c_int32, _P, c_int32, _P, _P, _P]),
     "cai_ckbd_indexes": (_I, [_P, c_int32, _P, c_int32, _F, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "cai_ckbd_dequantize": (_I, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),
+    "cai_code_front": (_I, [_P, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, _F, c_int32, c_int32, c_int32,
+                            c_int32, _P, c_int32, _P, _P, _P]),
+    "cai_code_indexes": (_I, [_P, c_int32, _P, c_int32, _F, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "cai_code_back": (_I, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),
 }
 
 

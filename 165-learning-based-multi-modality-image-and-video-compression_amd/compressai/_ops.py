@@ -2314,6 +2314,94 @@ def ckbd_dequantize(symbols, means, parity: int, y_hat):
                 "ckbd_dequantize", "ckbd_dequantize_kernel", 0, 6.0 * B * H * W * C, torch.float32)
 
 
+# ---------------------------------------------------------------------------
+# the coding front end / back end (csrc/code_front.hip): pixel-major latent <-> the host coder's NCHW integers
+# ---------------------------------------------------------------------------
+def _code_f32(t: torch.Tensor, shape=None) -> Tuple[torch.Tensor, int]:
+    _check_cuda(t)
+    if t.dim() != 4 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"coding front end: expected a 4-D tensor of shape {shape}, got {tuple(t.shape)}")
+    ld = pixel_major_ld(t)
+    if t.dtype == torch.float32 and ld is not None:
+        return t, ld        # any pitch and alignment: the kernels fall back to scalar accesses on their own
+    return to_pm(t, torch.float32, 1)
+
+
+def _code_ints(t: torch.Tensor, n: int, name: str) -> torch.Tensor:
+    _check_cuda(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"coding front end: {name} must be a dense int32 tensor of {n} elements")
+    return t
+
+
+def _code_channel_means(means: torch.Tensor, C: int) -> torch.Tensor:
+    m = means.detach().float().reshape(-1).contiguous()
+    _check_cuda(m)
+    if m.numel() != C:
+        raise ValueError(f"coding front end: {m.numel()} per-channel means for {C} channels")
+    return m
+
+
+def code_front(x, scales, means, scale_table, scale_bound: float, symbols, indexes) -> torch.Tensor:
+    """GaussianConditional front end (cai_code_front): x, scales, means [B, C, H, W] -> symbols / indexes (int32
+    [B, C H W], the coder's order, written in place) and x_hat (a new pixel-major fp32 tensor)."""
+    B, C, H, W = x.shape
+    xp, xld = _code_f32(x)
+    sp, sld = _code_f32(scales, x.shape)
+    mp, mld = _code_f32(means, x.shape)
+    n = B * H * W * C
+    _code_ints(symbols, n, "symbols"), _code_ints(indexes, n, "indexes")
+    tab = scale_table.detach().float().contiguous()
+    _check_cuda(tab)
+    x_hat = empty_pm(B, C, H, W, torch.float32, x.device)
+    _ledger.run(lambda: lib.cai_code_front(_p(xp), xld, _p(sp), sld, _p(mp), mld, _p(tab), tab.numel(),
+                                           float(scale_bound), B, H, W, C, _p(x_hat), C, _p(symbols), _p(indexes),
+                                           _stream()),
+                "code_front", "code_front_kernel", 0, 24.0 * n, torch.float32)
+    return x_hat
+
+
+def code_front_channels(x, means, symbols, indexes) -> torch.Tensor:
+    """EntropyBottleneck front end: per-channel means [C], indexes = the channel (cai_code_front, scales NULL)."""
+    B, C, H, W = x.shape
+    xp, xld = _code_f32(x)
+    m = _code_channel_means(means, C)
+    n = B * H * W * C
+    _code_ints(symbols, n, "symbols"), _code_ints(indexes, n, "indexes")
+    x_hat = empty_pm(B, C, H, W, torch.float32, x.device)
+    _ledger.run(lambda: lib.cai_code_front(_p(xp), xld, None, 0, _p(m), 0, None, 0, 0.0, B, H, W, C, _p(x_hat), C,
+                                           _p(symbols), _p(indexes), _stream()),
+                "code_front", "code_front_kernel", 0, 16.0 * n, torch.float32)
+    return x_hat
+
+
+def code_indexes(scales, scale_table, scale_bound: float, indexes) -> None:
+    """Decoder, before the coder (cai_code_indexes): build_indexes(scales) in the coder's order."""
+    B, C, H, W = scales.shape
+    sp, sld = _code_f32(scales)
+    _code_ints(indexes, B * H * W * C, "indexes")
+    tab = scale_table.detach().float().contiguous()
+    _check_cuda(tab)
+    _ledger.run(lambda: lib.cai_code_indexes(_p(sp), sld, _p(tab), tab.numel(), float(scale_bound), B, H, W, C,
+                                             _p(indexes), _stream()),
+                "code_indexes", "code_front_kernel", 0, 8.0 * B * H * W * C, torch.float32)
+
+
+def code_back(symbols, means, shape) -> torch.Tensor:
+    """Decoder, after the coder (cai_code_back): x_hat = float(symbols) + means, pixel-major fp32 of `shape`
+    [B, C, H, W]; means of that shape, or a per-channel vector of C elements."""
+    B, C, H, W = shape
+    _code_ints(symbols, B * H * W * C, "symbols")
+    if means.dim() == 4 and tuple(means.shape) == tuple(shape):
+        mp, mld = _code_f32(means)
+    else:
+        mp, mld = _code_channel_means(means, C), 0
+    x_hat = empty_pm(B, C, H, W, torch.float32, symbols.device)
+    _ledger.run(lambda: lib.cai_code_back(_p(symbols), _p(mp), mld, B, H, W, C, _p(x_hat), C, _stream()),
+                "code_back", "code_back_kernel", 0, 12.0 * B * H * W * C, torch.float32)
+    return x_hat
+
+
 def _like_logical(d: torch.Tensor, buf: torch.Tensor, shape) -> torch.Tensor:
     """d has buf's memory layout; return it as a tensor of the likelihood's logical shape."""
     if tuple(buf.shape) == tuple(shape):

@@ -25,11 +25,19 @@ module's device and quantizes them to CDF tables in libcai_coder.so
 the quantize kernel (SYMBOLS mode) and codes one rANS stream per image on
 host threads (cai_rans_encode_batch), byte-identical to compressai.ans;
 decompress() decodes them (cai_rans_decode_batch) and dequantizes.
+
+compress_deferred() / decompress_deferred() are the same coding with the host
+part left pending: one launch of the coding front end (csrc/code_front.hip)
+writes symbols and indexes in the coder's order plus x_hat, non-blocking copies
+take the integers to pinned memory, and the returned pending object runs the
+host coder when its result is asked for -- on a worker thread when a frame
+pipeline (utils/video/pipeline.py) runs it.  Same bytes as compress().
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import threading
 from typing import Any, Callable, List, Optional, Tuple, Union
 
 import numpy as np
@@ -40,8 +48,8 @@ import scipy.stats
 
 from .. import _coder
 from .._native import F32, NOISE_STATE_WORDS, Q_DEQUANTIZE, Q_NOISE, Q_SYMBOLS, lib
-from .._ops import (BottleneckAuxFn, BottleneckFn, DeviceDraw, GaussianFn, _check_cuda, _p, _stream, as_rows, dcode,
-                    empty_rows_like, noise_src)
+from .._ops import (BottleneckAuxFn, BottleneckFn, DeviceDraw, GaussianFn, _check_cuda, _p, _stream, as_rows,
+                    code_back, code_front, code_front_channels, code_indexes, dcode, empty_rows_like, noise_src)
 from ..ops import LowerBound
 
 __all__ = ["EntropyModel", "EntropyBottleneck", "GaussianConditional", "set_noise_source", "seed_noise"]
@@ -169,6 +177,114 @@ class _QuantizeFn(torch.autograd.Function):
         return torch.zeros_like(g), gm, None, None
 
 
+# ---------------------------------------------------------------------------
+# deferred coding: the device side returns at once, the host coder runs when (and where) the pending object is run
+# ---------------------------------------------------------------------------
+def _staging(slot, key, numel: int) -> torch.Tensor:
+    """A pinned int32 host tensor of numel elements: the slot's (utils.video.pipeline.StagingSlot), or a new one."""
+    if slot is not None:
+        return slot.buffer(key, numel)
+    return torch.empty(max(1, numel), dtype=torch.int32, pin_memory=True)[:numel]
+
+
+def _fused_coding(*ts) -> bool:
+    """The coding front / back end kernels take 4-D fp32 CUDA tensors; anything else goes through the composed ops."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.float32 for t in ts)
+
+
+class _TablesCache:
+    """An entropy model's host tables and what they were built from.  The tables hold raw pointers into their own
+    arrays, so a copy or a pickle of the module starts with an empty cache instead of a copied one."""
+
+    __slots__ = ("key", "tables")
+
+    def __init__(self, key=None, tables=None):
+        self.key, self.tables = key, tables
+
+    def __deepcopy__(self, memo):
+        return _TablesCache()
+
+    def __reduce__(self):
+        return (_TablesCache, ())
+
+
+class _Pending:
+    """A host-coder job.  ``run()`` may be called from a worker thread: it waits for the device event, then calls
+    libcai_coder through ctypes -- no launch, no allocation on the device, no tensor operation.  ``result()`` runs
+    it on the calling thread if nobody has, and re-raises what it raised."""
+
+    def __init__(self):
+        self._lock = threading.Lock()       # run() from two threads: the second waits and takes the first's outcome
+        self._done = False
+        self._value = None
+        self._error: Optional[BaseException] = None
+
+    def _work(self):
+        raise NotImplementedError
+
+    def run(self):
+        with self._lock:
+            if not self._done:
+                try:
+                    self._value = self._work()
+                except BaseException as e:      # kept for result(); a pool re-raises it from its future as well
+                    self._error = e
+                self._done = True
+        if self._error is not None:
+            raise self._error
+        return self._value
+
+    def result(self):
+        return self.run()
+
+
+class PendingStrings(_Pending):
+    """The strings of one deferred ``compress``: symbols and indexes are on their way into pinned host memory
+    (``event`` follows the copies); ``result()`` is the list of ``bytes``, one per batch element."""
+
+    def __init__(self, sym: torch.Tensor, idx: torch.Tensor, event, tables: "_coder.Tables", nstreams: int,
+                 threads: int = 1):
+        super().__init__()
+        self._host = (sym, idx)             # pinned tensors, kept alive until the coder has read them
+        self._np = (sym.numpy(), idx.numpy())     # views made here: the worker touches no tensor
+        self._event, self._tables, self._n, self._threads = event, tables, int(nstreams), int(threads)
+
+    def _work(self):
+        if self._event is not None:
+            self._event.synchronize()
+        sym, idx = self._np
+        return _coder.encode_streams(sym, idx, self._tables, self._n, self._threads)
+
+
+class PendingSymbols(_Pending):
+    """The symbols of one deferred ``decompress``: ``run()`` decodes the strings into pinned host memory (the
+    indexes arrive there behind ``event``); ``finish()`` -- main thread -- copies them to the device and dequantizes."""
+
+    def __init__(self, strings, idx: torch.Tensor, out: torch.Tensor, event, tables: "_coder.Tables", finish,
+                 threads: int = 1, slot=None):
+        super().__init__()
+        self._slot = slot
+        self._strings = [bytes(s) for s in strings]
+        self._idx, self._out, self._event, self._tables = idx, out, event, tables
+        self._np = (idx.numpy(), out.numpy())     # views made here: the worker touches no tensor
+        self._finish, self._threads = finish, int(threads)
+
+    def _work(self):
+        if self._event is not None:
+            self._event.synchronize()
+        _coder.decode_streams_into(self._strings, self._np[0], self._tables, self._np[1], self._threads)
+        return True
+
+    def finish(self) -> torch.Tensor:
+        self.result()
+        x_hat = self._finish(self._out)
+        if self._slot is not None and x_hat.is_cuda:
+            # the staging slot may be written again only after the copy issued above has read it
+            self._slot.busy = torch.cuda.Event(blocking=True)
+            self._slot.busy.record()
+        return x_hat
+
+
 class EntropyModel(nn.Module):
     def __init__(self, likelihood_bound: float = 1e-9, entropy_coder: Optional[str] = None,
                  entropy_coder_precision: int = 16):
@@ -264,6 +380,88 @@ class EntropyModel(nn.Module):
     def _tables(self) -> "_coder.Tables":
         return _coder.Tables(self._quantized_cdf.cpu().numpy(), self._cdf_length.reshape(-1).cpu().numpy(),
                              self._offset.reshape(-1).cpu().numpy())
+
+    def _host_tables(self) -> "_coder.Tables":
+        """_tables(), cached: the three CDF buffers are copied to the host once and again only after one of them
+        was replaced (update(), load_state_dict's resize, .to()) or written in place (load_state_dict's copy_).
+        The cache holds the tensors it was built from, so an `is` test cannot be fooled by a recycled id."""
+        bufs = (self._quantized_cdf, self._cdf_length, self._offset)
+        cache = self.__dict__.get("_tables_cache")
+        if cache is not None and cache.key is not None and all(a is b and a._version == v
+                                                               for a, (b, v) in zip(bufs, cache.key)):
+            return cache.tables
+        tables = self._tables()
+        self.__dict__["_tables_cache"] = _TablesCache([(t, t._version) for t in bufs], tables)
+        return tables
+
+    def _check_coding_state(self):
+        self._check_cdf_size()
+        self._check_cdf_length()
+        self._check_offsets_size()
+
+    def _stage_out(self, symbols: torch.Tensor, indexes: torch.Tensor, slot, key, threads: int) -> PendingStrings:
+        """Non-blocking copies of dense int32 [B, n] device symbols / indexes into pinned memory, an event behind
+        them, and the pending strings."""
+        B, n = symbols.shape
+        host = [_staging(slot, (key, name), B * n).reshape(B, n) for name in ("symbols", "indexes")]
+        host[0].copy_(symbols, non_blocking=True)
+        host[1].copy_(indexes, non_blocking=True)
+        event = torch.cuda.Event(blocking=True)     # a waiting worker sleeps, it does not spin
+        event.record()
+        return PendingStrings(host[0], host[1], event, self._host_tables(), B, threads)
+
+    def _compress_deferred(self, inputs, scales, means, slot=None, key=None, threads: int = 1):
+        """(x_hat, PendingStrings).  scales given: the GaussianConditional's form (indexes from the scales, means per
+        element); scales None: the EntropyBottleneck's (means = the per-channel medians [C], index = channel).
+        4-D fp32 CUDA inputs take one launch of the coding front end; other inputs take the composed ops, so that
+        their bytes stay those of compress()."""
+        _check_cuda(inputs)
+        if inputs.dim() < 2:
+            raise ValueError("Invalid `inputs` size. Expected a tensor with at least 2 dimensions.")
+        self._check_coding_state()
+        B = inputs.size(0)
+        per_channel = scales is None
+        if _fused_coding(inputs) and (per_channel or _fused_coding(scales, means)):
+            n = inputs.numel() // B
+            symbols = torch.empty((B, n), dtype=torch.int32, device=inputs.device)
+            indexes = torch.empty((B, n), dtype=torch.int32, device=inputs.device)
+            if per_channel:
+                x_hat = code_front_channels(inputs, means, symbols, indexes)
+            else:
+                x_hat = code_front(inputs, scales, means, self.scale_table, self._scale_bound_value, symbols, indexes)
+        else:
+            if per_channel:
+                indexes = self._build_indexes(inputs.size()).to(inputs.device)
+                medians = self._extend_ndims(means, inputs.dim() - 2).expand(B, *([-1] * (inputs.dim() - 1)))
+                sym = self.quantize(inputs, "symbols", medians)
+                x_hat = self.dequantize(sym, medians)        # what decompress(compress(x)) returns
+            else:
+                indexes = self.build_indexes(scales)
+                sym = self.quantize(inputs, "symbols", means)
+                x_hat = self.quantize(inputs, "dequantize", means)
+            symbols = sym.reshape(B, -1).contiguous()
+            indexes = indexes.reshape(B, -1).int().contiguous()
+        return x_hat, self._stage_out(symbols, indexes, slot, key, threads)
+
+    def _decompress_deferred(self, strings, indexes: torch.Tensor, finish, slot=None, key=None,
+                             threads: int = 1) -> PendingSymbols:
+        """indexes: dense int32 [B, n] on the device (or a host tensor); finish(host symbols [B, n]) -> x_hat."""
+        if not isinstance(strings, (tuple, list)):
+            raise ValueError("Invalid `strings` parameter type.")
+        if len(strings) != indexes.size(0):
+            raise ValueError("Invalid strings or indexes parameters")
+        self._check_coding_state()
+        B, n = indexes.shape
+        event = None
+        if indexes.is_cuda:
+            host_idx = _staging(slot, (key, "indexes"), B * n).reshape(B, n)
+            host_idx.copy_(indexes, non_blocking=True)
+            event = torch.cuda.Event(blocking=True)     # a waiting worker sleeps, it does not spin
+            event.record()
+        else:
+            host_idx = indexes
+        out = _staging(slot, (key, "symbols"), B * n).reshape(B, n)
+        return PendingSymbols(strings, host_idx, out, event, self._host_tables(), finish, threads, slot)
 
     def compress(self, inputs, indexes, means=None):
         """entropy_models.py:237-270: one rANS string per batch element."""
@@ -428,6 +626,44 @@ class EntropyBottleneck(EntropyModel):
         medians = medians.expand(len(strings), *([-1] * (len(size) + 1)))
         return super().decompress(strings, indexes, medians.dtype, medians)
 
+    def compress_deferred(self, x, slot=None, key="z", threads: int = 1):
+        """(x_hat, PendingStrings): x_hat -- what decompress(compress(x), x.size()[2:]) returns -- comes from the
+        device at once (the coding front end for 4-D fp32 inputs); pending.result() is compress(x)."""
+        return self._compress_deferred(x, None, self._get_medians().detach().reshape(-1), slot, key, threads)
+
+    def _host_indexes(self, B: int, size) -> torch.Tensor:
+        """_build_indexes on the host, int32 [B, C prod(size)], cached per shape: no device round trip."""
+        C = int(self._quantized_cdf.size(0))
+        shape = (int(B), C, int(np.prod(size)) if len(size) else 1)
+        cache = self.__dict__.setdefault("_host_index_cache", {})
+        idx = cache.get(shape)
+        if idx is None:
+            if len(cache) > 8:
+                cache.clear()
+            a = np.broadcast_to(np.arange(C, dtype=np.int32)[None, :, None], shape)
+            idx = cache[shape] = torch.from_numpy(np.array(a).reshape(shape[0], -1))     # a copy: writable, dense
+        return idx
+
+    def decompress_host(self, strings, size, slot=None, key="z", threads: Optional[int] = None):
+        """decompress(strings, size) without a device round trip before the coder: host-built indexes, cached
+        tables, the decoded symbols through pinned memory and the coding back end (2-D sizes)."""
+        size = tuple(int(s) for s in size)
+        B = len(strings)
+        C = int(self._quantized_cdf.size(0))
+        device = self._quantized_cdf.device
+        medians = self._get_medians().detach()
+
+        def finish(host):
+            sym = host.to(device, non_blocking=True)
+            if len(size) == 2 and sym.is_cuda and medians.dtype == torch.float32:
+                return code_back(sym, medians.reshape(-1), (B, C) + size)
+            m = self._extend_ndims(medians, len(size)).expand(B, *([-1] * (len(size) + 1)))
+            return self.dequantize(sym.reshape((B, C) + size), m, m.dtype)
+
+        if threads is None:
+            threads = _coder.default_threads()
+        return self._decompress_deferred(strings, self._host_indexes(B, size), finish, slot, key, threads).finish()
+
 
 class GaussianConditional(EntropyModel):
     def __init__(self, scale_table: Optional[Union[List, Tuple]], *args: Any, scale_bound: float = 0.11,
@@ -485,6 +721,38 @@ class GaussianConditional(EntropyModel):
         for s in self.scale_table[:-1]:
             indexes -= (scales <= s).int()
         return indexes
+
+    def compress_deferred(self, inputs, scales, means, slot=None, key="y", threads: int = 1):
+        """(x_hat, PendingStrings): x_hat = quantize(inputs, "dequantize", means) at once; pending.result() is
+        compress(inputs, build_indexes(scales), means).  4-D fp32 inputs: one launch of the coding front end."""
+        if scales.size() != inputs.size() or means is None or means.size() != inputs.size():
+            raise ValueError("`inputs`, `scales` and `means` should have the same size.")
+        return self._compress_deferred(inputs, scales, means, slot, key, threads)
+
+    def decompress_deferred(self, strings, scales, means, dtype: torch.dtype = torch.float, slot=None, key="y",
+                            threads: int = 1) -> PendingSymbols:
+        """The pending form of decompress(strings, build_indexes(scales), dtype, means): the index launch and the
+        copy of the indexes are issued here, ``run()`` decodes on whichever thread calls it, ``finish()`` (main
+        thread) copies the symbols to the device and returns x_hat."""
+        _check_cuda(scales, means)
+        if means is None or means.size() != scales.size():
+            raise ValueError("Invalid means or indexes parameters")
+        B = scales.size(0)
+        device = scales.device
+        if _fused_coding(scales, means):
+            shape = tuple(scales.shape)
+            indexes = torch.empty((B, scales.numel() // B), dtype=torch.int32, device=device)
+            code_indexes(scales, self.scale_table, self._scale_bound_value, indexes)
+
+            def finish(host):
+                return code_back(host.to(device, non_blocking=True), means, shape)
+        else:
+            full = self.build_indexes(scales)
+            indexes = full.reshape(B, -1).int().contiguous()
+
+            def finish(host):
+                return self.dequantize(host.to(device, non_blocking=True).reshape(full.size()), means, dtype)
+        return self._decompress_deferred(strings, indexes, finish, slot, key, threads)
 
     @staticmethod
     def _standardized_cumulative(inputs: torch.Tensor) -> torch.Tensor:

@@ -19,6 +19,11 @@ motion decoder's output in place (no chunk copies) and, on the encoder side, wri
 ``y_hat = round(y - means) + means`` rounds in training too: one launch of the quantize kernel whose gradient goes
 to ``y`` alone (the two ``means`` terms of the straight-through form cancel).
 
+Coding can run with several frames in flight (``compress(frames, frames_in_flight=W)``, the ``*_deferred`` encoders
+and the ``decode_*_begin`` / ``PendingDecode.finish`` halves): the device side of a frame returns at once and the host
+coder of up to W frames runs on worker threads (``utils/video/pipeline.py``).  The strings stay one serial rANS state
+each, byte for byte those of W = 1; W = 1 is the code path above, unchanged.
+
 Frames must have H and W that are multiples of 128 (four stride-2 stages, three more in the hyperprior); other
 sizes raise ``ValueError`` before anything is launched.
 """
@@ -34,6 +39,7 @@ from ..._prepack import prepacked_forward
 from ...entropy_models import GaussianConditional
 from ...entropy_models.entropy_models import _QuantizeFn
 from ...layers import QReLU, Sequential
+from ...utils.video.pipeline import StagingRing, check_frames_in_flight, run_ordered
 from ..google import CompressionModel, get_scale_table
 from ..utils import conv, deconv, update_registered_buffers
 
@@ -50,7 +56,7 @@ _TABLE = {
     "motion": (6, LATENT, 3, "motion"),           # cat(x_cur, x_ref) in; flow x, flow y and scale out
 }
 
-TRAIN, ENCODE, DECODE = "train", "encode", "decode"
+TRAIN, ENCODE, DECODE, ENCODE_DEFERRED = "train", "encode", "decode", "encode-deferred"
 
 
 def _chain(layer, widths):
@@ -132,6 +138,80 @@ class _StreamPrior(CompressionModel):
         gc = self.gaussian_conditional
         return gc.decompress(strings[0], gc.build_indexes(scales), z_hat.dtype, means)
 
+    # ---- deferred forms: the device side returns at once, the host coder runs behind it (frames in flight) ----
+    def compress_deferred(self, y, slot=None, key=""):
+        """(y_hat, _PendingStream): compress(y) without waiting for the host.  z_hat comes from the coding front
+        end (the integers the z strings will hold, plus the medians), so there is no host round trip for z; the
+        hyper decoders run on it as in compress()."""
+        z = self.hyper_encoder(y)
+        grid = z.size()[-2:]
+        z_hat, coded_z = self.entropy_bottleneck.compress_deferred(z, slot, (key, "z"))
+        scales, means = self._entropy_params(z_hat)
+        y_hat, coded_y = self.gaussian_conditional.compress_deferred(y, scales, means, slot, (key, "y"))
+        return y_hat, _PendingStream([coded_y, coded_z], grid)
+
+    def decompress_begin(self, strings, shape, slot=None, key=""):
+        """First half of decompress(): the z strings are decoded here (they are small and everything else waits for
+        them), the hyper decoders and the index launch follow, and the y strings are left pending.  ``jobs()`` of
+        the result go to the pool; its ``finish()`` returns y_hat."""
+        if not isinstance(strings, list) or len(strings) != 2:
+            raise ValueError("a stream is coded as [y strings, z strings]")
+        z_hat = self.entropy_bottleneck.decompress_host(strings[1], shape, slot, (key, "z"))
+        scales, means = self._entropy_params(z_hat)
+        return self.gaussian_conditional.decompress_deferred(strings[0], scales, means, z_hat.dtype, slot, (key, "y"))
+
+
+class _PendingStream:
+    """The [y strings, z strings] of one stream, pending."""
+
+    def __init__(self, pending, grid):
+        self.pending, self.grid = pending, grid
+
+    def jobs(self):
+        return [p.run for p in self.pending]
+
+    def result(self):
+        return {"strings": [p.result() for p in self.pending], "shape": self.grid}
+
+
+class PendingFrame:
+    """The side information of one deferred encode: ``jobs()`` are the host-coder calls (any thread), ``result()``
+    the ``{"strings", "shape"}`` dictionary encode_keyframe / encode_inter return."""
+
+    def __init__(self, streams, inter: bool):
+        self._streams, self._inter = streams, inter
+
+    def jobs(self):
+        return [j for s in self._streams.values() for j in s.jobs()]
+
+    def result(self):
+        side = {k: s.result() for k, s in self._streams.items()}
+        if not self._inter:
+            return side["keyframe"]
+        return {field: {k: v[field] for k, v in side.items()} for field in ("strings", "shape")}
+
+
+class PendingDecode:
+    """One frame between the two halves of its decode: ``jobs()`` decode the y strings (any thread);
+    ``finish(x_ref)`` -- main thread, in frame order -- runs the back ends, the synthesis nets, the warp and the add."""
+
+    def __init__(self, net, latents):
+        self._net, self._latents = net, latents
+
+    def jobs(self):
+        return [p.run for p in self._latents.values()]
+
+    def finish(self, x_ref=None):
+        net, lat = self._net, self._latents
+        if "keyframe" in lat:
+            return net.img_decoder(lat["keyframe"].finish())
+        if x_ref is None:
+            raise ValueError("an inter frame needs its reference")
+        y_m_hat = lat["motion"].finish()
+        x_pred = net._predict(x_ref, net.motion_decoder(y_m_hat))
+        y_r_hat = lat["residual"].finish()
+        return x_pred + net.res_decoder(CatFn.apply(y_r_hat, y_m_hat))
+
 
 def _want_list(*values):
     for v in values:
@@ -178,35 +258,38 @@ class ScaleSpaceFlow(nn.Module):
         with prepacked_forward(self):
             return super().__call__(frames, *args, **kwargs)
 
-    def _latent(self, prefix, mode, y=None, coded=None):
-        """(y_hat, side information) of one stream: likelihoods (TRAIN), strings + shape (ENCODE), None (DECODE)."""
+    def _latent(self, prefix, mode, y=None, coded=None, slot=None):
+        """(y_hat, side information) of one stream: likelihoods (TRAIN), strings + shape (ENCODE), the same pending
+        (ENCODE_DEFERRED), None (DECODE)."""
         prior = getattr(self, f"{prefix}_hyperprior")
         if mode == TRAIN:
             return prior(y)
+        if mode == ENCODE_DEFERRED:
+            return prior.compress_deferred(y, slot, prefix)
         if mode == ENCODE:
             return prior.compress(y)
         return prior.decompress(*coded), None
 
-    def _key_frame(self, mode, x=None, coded=None):
+    def _key_frame(self, mode, x=None, coded=None, slot=None):
         y = None if mode == DECODE else self.img_encoder(x)
-        y_hat, side = self._latent("img", mode, y, coded)
+        y_hat, side = self._latent("img", mode, y, coded, slot)
         return self.img_decoder(y_hat), side
 
-    def _inter_frame(self, mode, x_ref, x_cur=None, coded=None):
+    def _inter_frame(self, mode, x_ref, x_cur=None, coded=None, slot=None):
         """One predicted frame.  coded (DECODE): ({"motion": strings, "residual": strings}, the same for shapes)."""
         def pick(key):
             return None if coded is None else (coded[0][key], coded[1][key])
 
         side = {}
         y_m = None if mode == DECODE else self.motion_encoder(torch.cat((x_cur, x_ref), dim=1))
-        y_m_hat, side["motion"] = self._latent("motion", mode, y_m, pick("motion"))
+        y_m_hat, side["motion"] = self._latent("motion", mode, y_m, pick("motion"), slot)
         motion_info = self.motion_decoder(y_m_hat)
         if mode == DECODE:
             x_pred, y_r = self._predict(x_ref, motion_info), None
         else:       # the prediction and x_cur - x_pred from one warp launch
             x_pred, x_res = self._predict(x_ref, motion_info, x_cur)
             y_r = self.res_encoder(x_res)
-        y_r_hat, side["residual"] = self._latent("res", mode, y_r, pick("residual"))
+        y_r_hat, side["residual"] = self._latent("res", mode, y_r, pick("residual"), slot)
         x_rec = x_pred + self.res_decoder(CatFn.apply(y_r_hat, y_m_hat))
         return x_rec, side
 
@@ -269,9 +352,74 @@ class ScaleSpaceFlow(nn.Module):
     def decode_inter(self, x_ref, strings, shapes):
         return self._inter_frame(DECODE, x_ref, coded=(strings, shapes))[0]
 
+    # ---- deferred coding (frames in flight): see utils/video/pipeline.py ----
+    def encode_keyframe_deferred(self, x, slot=None):
+        """(x_rec, PendingFrame): encode_keyframe without waiting for the host coder; ``pending.result()`` is
+        encode_keyframe's dictionary.  slot: a pipeline.StagingSlot for the pinned buffers (None: new ones)."""
+        x_rec, side = self._key_frame(ENCODE_DEFERRED, x, slot=slot)
+        return x_rec, PendingFrame({"keyframe": side}, inter=False)
+
+    def encode_inter_deferred(self, x_cur, x_ref, slot=None):
+        """(x_rec, PendingFrame): encode_inter without waiting for the host coder."""
+        x_rec, side = self._inter_frame(ENCODE_DEFERRED, x_ref, x_cur, slot=slot)
+        return x_rec, PendingFrame(side, inter=True)
+
+    def decode_keyframe_begin(self, strings, shape, slot=None):
+        """First half of decode_keyframe: everything up to "the y strings are queued"; PendingDecode.finish() is
+        the second.  The hyper-decoder launches are decode_keyframe's, at its shapes."""
+        return PendingDecode(self, {"keyframe": self.img_hyperprior.decompress_begin(strings, shape, slot, "img")})
+
+    def decode_inter_begin(self, strings, shapes, slot=None):
+        """First half of decode_inter: it needs no reconstruction, so it can run ahead of the frames before it;
+        PendingDecode.finish(x_ref) is the second half."""
+        return PendingDecode(self, {
+            "motion": self.motion_hyperprior.decompress_begin(strings["motion"], shapes["motion"], slot, "motion"),
+            "residual": self.res_hyperprior.decompress_begin(strings["residual"], shapes["residual"], slot, "res")})
+
+    def _compress_in_flight(self, frames, frames_in_flight):
+        ring = StagingRing(frames_in_flight)
+        strings, shapes, ref = [], [], [None]
+
+        def issue(i):
+            slot = ring.slot(i)
+            if i == 0:
+                ref[0], pending = self.encode_keyframe_deferred(frames[i], slot)
+            else:
+                ref[0], pending = self.encode_inter_deferred(frames[i], ref[0], slot)
+            return pending, pending.jobs()
+
+        def deliver(i, pending, _):
+            info = pending.result()
+            strings.append(info["strings"])
+            shapes.append(info["shape"])
+
+        run_ordered(len(frames), frames_in_flight, issue, deliver)
+        return strings, shapes
+
+    def _decompress_in_flight(self, strings, shapes, frames_in_flight):
+        ring = StagingRing(frames_in_flight)
+        frames = []
+
+        def issue(i):
+            slot = ring.slot(i)
+            begin = self.decode_keyframe_begin if i == 0 else self.decode_inter_begin
+            pending = begin(strings[i], shapes[i], slot)
+            return pending, pending.jobs()
+
+        def deliver(i, pending, _):
+            frames.append(pending.finish(frames[-1] if frames else None))
+
+        run_ordered(len(strings), frames_in_flight, issue, deliver)
+        return frames
+
     @torch.no_grad()
-    def compress(self, frames):
+    def compress(self, frames, frames_in_flight: int = 1):
+        """frames_in_flight = W > 1: the host coder of up to W frames runs on worker threads behind the device
+        work of the frames after them; the strings are those of W = 1, byte for byte."""
         self._check_frames(frames)
+        if check_frames_in_flight(frames_in_flight) > 1:
+            with prepacked_forward(self):
+                return self._compress_in_flight(frames, frames_in_flight)
         strings, shapes = [], []
         with prepacked_forward(self):
             x_ref = None
@@ -282,10 +430,13 @@ class ScaleSpaceFlow(nn.Module):
         return strings, shapes
 
     @torch.no_grad()
-    def decompress(self, strings, shapes):
+    def decompress(self, strings, shapes, frames_in_flight: int = 1):
         _want_list(strings, shapes)
         if len(strings) != len(shapes):
             raise ValueError(f"{len(strings)} coded frames but {len(shapes)} shapes")
+        if check_frames_in_flight(frames_in_flight) > 1:
+            with prepacked_forward(self):
+                return self._decompress_in_flight(strings, shapes, frames_in_flight)
         frames = []
         with prepacked_forward(self):
             for s, sh in zip(strings, shapes):

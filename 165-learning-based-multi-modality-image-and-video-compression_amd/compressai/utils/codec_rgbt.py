@@ -330,12 +330,14 @@ def read_video_header(fd: IO[bytes]) -> VideoHeader:
 
 
 def encode_video(input: str, net, output: str, metric: str = "mse", quality: int = 3,
-                 num_frames: int = -1) -> Dict[str, float]:
+                 num_frames: int = -1, frames_in_flight: int = 1) -> Dict[str, float]:
     """Code the first ``num_frames`` frames (all if negative) of the raw 4:2:0 file ``input`` into ``output``.
-    Returns the file's bpp, the frame count and the mean encoding time per frame (codec_rgbt.py:389-451)."""
+    Returns the file's bpp, the frame count and the mean encoding time per frame (codec_rgbt.py:389-451).
+    ``frames_in_flight`` > 1 codes that many frames' strings on host threads behind the device; same file."""
     if Path(input).suffix != ".yuv":
         raise NotImplementedError(f"Unsupported video file extension: {Path(input).suffix}")
     container = _container()
+    container.check_frames_in_flight(frames_in_flight)      # before the output file is created
     org_seq = container._open(input)
     if num_frames < 0:
         num_frames = len(org_seq)
@@ -344,17 +346,23 @@ def encode_video(input: str, net, output: str, metric: str = "mse", quality: int
     stamps = [time.time()]
     with Path(output).open("wb") as f:
         write_uchars(f, get_header("ssf2020", metric, quality))
-        container.encode_frames(net, org_seq, f, num_frames, per_frame=lambda *_: stamps.append(time.time()))
+        container.encode_frames(net, org_seq, f, num_frames, per_frame=lambda *_: stamps.append(time.time()),
+                                frames_in_flight=frames_in_flight)
+        if frames_in_flight > 1 and num_frames:
+            stamps[-1] = time.time()        # the last frames' strings were written after their per_frame call
     h, w = org_seq.height, org_seq.width
     org_seq.close()
     return {"bpp": Path(output).stat().st_size * 8.0 / (h * w * max(num_frames, 1)), "frames": num_frames,
             "avg_frm_enc_time": (stamps[-1] - stamps[0]) / max(num_frames, 1)}
 
 
-def decode_video(inputpath: str, net, output: Optional[str] = None) -> Tuple[VideoHeader, Optional[torch.Tensor]]:
+def decode_video(inputpath: str, net, output: Optional[str] = None,
+                 frames_in_flight: int = 1) -> Tuple[VideoHeader, Optional[torch.Tensor]]:
     """Decode ``inputpath``.  With ``output`` ending in .yuv every frame is appended to it as integer 4:2:0 planes
     (one launch and one copy per frame, levels rounded to nearest); any other ``output`` receives the last frame as
-    an image.  Returns the header and the last frame [1, C, H, W] in [0, 1] (codec_rgbt.py:557-598)."""
+    an image.  Returns the header and the last frame [1, C, H, W] in [0, 1] (codec_rgbt.py:557-598).
+    ``frames_in_flight`` > 1: the strings of that many frames are decoded on host threads ahead of the
+    reconstruction chain; same frames."""
     from compressai.utils.video import frames
 
     container = _container()
@@ -371,7 +379,7 @@ def decode_video(inputpath: str, net, output: Optional[str] = None) -> Tuple[Vid
                 if i == hdr.frames - 1:
                     last.append(container.crop(x_rec, padding, h, w))
 
-            container.decode_frames(net, f, h, w, hdr.frames, emit)
+            container.decode_frames(net, f, h, w, hdr.frames, emit, frames_in_flight=frames_in_flight)
         finally:
             if fout is not None:
                 fout.close()
@@ -426,6 +434,9 @@ def _common_args(p: argparse.ArgumentParser):
     p.add_argument("--ar-backend", choices=("serial", "fused"), default="serial",
                    help="autoregressive coding of the context models: the per-pixel loop, or the whole scan in one "
                         "kernel launch; a stream must be decoded with the backend that encoded it")
+    p.add_argument("--frames-in-flight", type=int, default=1, metavar="N",
+                   help="video: code up to N frames' strings on host threads behind the device (same bytes; N "
+                        "frames of delay and staging memory)")
 
 
 def encode_parser() -> argparse.ArgumentParser:
@@ -454,7 +465,7 @@ def encode(argv):
     device = _device(a)
     if a.model in VIDEO_MODELS:
         net = _load_video_net(a.model, a.path, device)
-        r = encode_video(a.input, net, a.output, a.metric, a.quality, a.num_of_frames)
+        r = encode_video(a.input, net, a.output, a.metric, a.quality, a.num_of_frames, a.frames_in_flight)
         print(f"{r['bpp']:.3f} bpp | {r['frames']} frames | {r['avg_frm_enc_time']:.2f}s per frame")
         return
     net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)
@@ -479,7 +490,7 @@ def decode(argv):
     device = _device(a)
     if a.model in VIDEO_MODELS:
         t = time.time()
-        hdr, _ = decode_video(a.input, _load_video_net(a.model, a.path, device), a.output)
+        hdr, _ = decode_video(a.input, _load_video_net(a.model, a.path, device), a.output, a.frames_in_flight)
         print(f"Decoded {hdr.frames} frames in {time.time() - t:.2f}s")
         return
     net = _load_nets(a.model, a.path, a.channel, device, a.ar_backend)

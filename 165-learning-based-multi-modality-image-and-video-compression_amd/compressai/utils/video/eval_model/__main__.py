@@ -37,6 +37,7 @@ from compressai._prepack import prepacked_forward
 from compressai.datasets import RawVideoSequence, VideoFormat
 from compressai.models.video import ScaleSpaceFlow
 from compressai.utils.video import frames
+from compressai.utils.video.pipeline import StagingRing, check_frames_in_flight, run_ordered
 from compressai.zoo import load_state_dict
 from compressai.zoo import video_models as pretrained_models
 
@@ -160,13 +161,23 @@ def _finish(results: Dict[str, list]) -> Dict[str, float]:
 
 @torch.no_grad()
 def encode_frames(net: nn.Module, org_seq: RawVideoSequence, f, num_frames: int, half: bool = False,
-                  per_frame=None) -> None:
+                  per_frame=None, frames_in_flight: int = 1) -> None:
     """Write the container of the first ``num_frames`` frames of ``org_seq`` to the open file ``f``: the header, then
     each frame's bodies.  ``per_frame(i, planes, org_q, x_rec, padding)`` is called after frame i is written, with
     its integer planes on the device, its RGB levels and the clamped reconstruction (the next reference: it must
-    not be changed).  The one encoder loop of this package: the evaluation and the codec CLI both run it."""
+    not be changed).  The one encoder loop of this package: the evaluation and the codec CLI both run it.
+
+    ``frames_in_flight = W > 1``: the device work of frame i + 1 is issued while the strings of the frames <= i are
+    still being coded on host threads, up to W frames deep (utils/video/pipeline.py).  The file's bytes are those of
+    W = 1.  Bodies are written and ``per_frame`` is called in frame order, but ``per_frame(i, ...)`` may then run
+    before body i reaches the file: it runs when frame i's device work has been issued."""
     device = next(net.parameters()).device
     bitdepth = org_seq.bitdepth
+    if check_frames_in_flight(frames_in_flight) > 1:
+        with prepacked_forward(net):
+            write_header(f, org_seq.height, org_seq.width, bitdepth, num_frames)
+            _encode_frames_in_flight(net, org_seq, f, num_frames, half, per_frame, frames_in_flight, device)
+        return
     with prepacked_forward(net):
         write_header(f, org_seq.height, org_seq.width, bitdepth, num_frames)
         x_rec = None
@@ -186,9 +197,38 @@ def encode_frames(net: nn.Module, org_seq: RawVideoSequence, f, num_frames: int,
                 per_frame(i, planes, org_q, x_rec, padding)
 
 
+def _encode_frames_in_flight(net, org_seq, f, num_frames, half, per_frame, frames_in_flight, device):
+    bitdepth = org_seq.bitdepth
+    ring = StagingRing(frames_in_flight)
+    ref = [None]
+
+    def issue(i):
+        planes = frames.to_planes(org_seq[i], device)
+        x_cur, padding, org_q = frames.yuv420_to_rgb(planes, bitdepth, UPSAMPLING, net.downsampling_factor)
+        with _autocast(half, device):
+            if i == 0:
+                x_rec, pending = net.encode_keyframe_deferred(x_cur, ring.slot(i))
+            else:
+                x_rec, pending = net.encode_inter_deferred(x_cur, ref[0], ring.slot(i))
+        ref[0] = x_rec = x_rec.float().clamp_(0, 1)
+        if per_frame is not None:
+            per_frame(i, planes, org_q, x_rec, padding)
+        return pending, pending.jobs()
+
+    def deliver(i, pending, _):
+        enc_info = pending.result()
+        if i == 0:
+            write_body(f, enc_info["shape"], enc_info["strings"])
+        else:
+            for key in ("motion", "residual"):
+                write_body(f, enc_info["shape"][key], enc_info["strings"][key])
+
+    run_ordered(num_frames, frames_in_flight, issue, deliver)
+
+
 @torch.no_grad()
 def eval_model(net: nn.Module, sequence: Path, binpath: Path, keep_binaries: bool = False,
-               half: bool = False) -> Dict[str, Any]:
+               half: bool = False, frames_in_flight: int = 1) -> Dict[str, Any]:
     """Code ``sequence`` into ``binpath``; the metrics of the encoder's reconstructions and the file's bit rate."""
     sequence, binpath = Path(sequence), Path(binpath)
     org_seq = _open(sequence)
@@ -201,7 +241,7 @@ def eval_model(net: nn.Module, sequence: Path, binpath: Path, keep_binaries: boo
 
     print(f" encoding {sequence.stem}", file=sys.stderr)
     with binpath.open("wb") as f:
-        encode_frames(net, org_seq, f, num_frames, half, measure)
+        encode_frames(net, org_seq, f, num_frames, half, measure, frames_in_flight)
     seq_results: Dict[str, Any] = _finish(results)
     seq_results["bitrate"] = float(filesize(binpath)) * 8 * float(org_seq.framerate) / (num_frames * 1000)
     if not keep_binaries:
@@ -239,12 +279,21 @@ def eval_model_entropy_estimation(net: nn.Module, sequence: Path, half: bool = F
 
 
 @torch.no_grad()
-def decode_frames(net: nn.Module, f, height: int, width: int, num_frames: int, per_frame, half: bool = False) -> None:
+def decode_frames(net: nn.Module, f, height: int, width: int, num_frames: int, per_frame, half: bool = False,
+                  frames_in_flight: int = 1) -> None:
     """Decode the ``num_frames`` frames that follow the header in the open file ``f``.  ``per_frame(i, x_rec,
     padding)`` is called with each clamped, still padded reconstruction (the next reference: it must not be
-    changed) and the (left, right, top, bottom) of the frame inside it."""
+    changed) and the (left, right, top, bottom) of the frame inside it.
+
+    ``frames_in_flight = W > 1``: the first half of the decode (read the bodies, decode z, hyper decoders, queue the
+    y strings on host threads) runs for the frames up to i + W - 1 before the second half of frame i (synthesis,
+    warp, add), which needs frame i - 1.  The frames are those of W = 1, bit for bit, and arrive in order."""
     device = next(net.parameters()).device
     Hp, Wp, padding = frames.pad_geometry(height, width, net.downsampling_factor)
+    if check_frames_in_flight(frames_in_flight) > 1:
+        with prepacked_forward(net):
+            _decode_frames_in_flight(net, f, num_frames, per_frame, half, frames_in_flight, device, (Hp, Wp), padding)
+        return
     with prepacked_forward(net):
         x_rec = None
         for i in range(num_frames):
@@ -262,20 +311,48 @@ def decode_frames(net: nn.Module, f, height: int, width: int, num_frames: int, p
             per_frame(i, x_rec, padding)
 
 
+def _decode_frames_in_flight(net, f, num_frames, per_frame, half, frames_in_flight, device, padded, padding):
+    ring = StagingRing(frames_in_flight)
+    ref = [None]
+
+    def issue(i):
+        with _autocast(half, device):
+            if i == 0:
+                strings, shape = read_body(f)
+                pending = net.decode_keyframe_begin(strings, shape, ring.slot(i))
+            else:
+                bodies = {key: read_body(f) for key in ("motion", "residual")}
+                pending = net.decode_inter_begin({k: b[0] for k, b in bodies.items()},
+                                                 {k: b[1] for k, b in bodies.items()}, ring.slot(i))
+        return pending, pending.jobs()
+
+    def deliver(i, pending, _):
+        with _autocast(half, device):
+            x_rec = pending.finish(ref[0])
+        ref[0] = x_rec = x_rec.float().clamp_(0, 1)
+        if tuple(x_rec.shape[-2:]) != padded:
+            raise ValueError(f"frame {i} decodes to {tuple(x_rec.shape[-2:])}, the header says "
+                             f"{padded[0]} x {padded[1]} padded")
+        per_frame(i, x_rec, padding)
+
+    run_ordered(num_frames, frames_in_flight, issue, deliver)
+
+
 def crop(x_rec: torch.Tensor, padding, height: int, width: int) -> torch.Tensor:
     left, _, top, _ = padding
     return x_rec[:, :, top:top + height, left:left + width].clone()
 
 
 @torch.no_grad()
-def decode_sequence(net: nn.Module, binpath: Path, half: bool = False) -> List[torch.Tensor]:
+def decode_sequence(net: nn.Module, binpath: Path, half: bool = False, frames_in_flight: int = 1) -> List[torch.Tensor]:
     """The frames a bitstream written by ``eval_model`` decodes to: [1, 3, H, W] each, cropped and clamped to
     [0, 1] (the clamped, uncropped frame is the next reference, as on the encoder side)."""
     out = []
     with Path(binpath).open("rb") as f:
         height, width, _, num_frames = read_header(f)
         decode_frames(net, f, height, width, num_frames,
-                      lambda i, x_rec, padding: out.append(crop(x_rec, padding, height, width)), half)
+                      lambda i, x_rec, padding: out.append(crop(x_rec, padding, height, width)), half,
+                      frames_in_flight)
     return out
 
 
@@ -295,7 +372,8 @@ def run_inference(filepaths, net: nn.Module, outputdir: Path, force: bool = Fals
             metrics = eval_model_entropy_estimation(net, filepath, half)
         else:
             sequence_bin = sequence_metrics_path.with_suffix(".bin")
-            metrics = eval_model(net, filepath, sequence_bin, bool(args.get("keep_binaries", False)), half)
+            metrics = eval_model(net, filepath, sequence_bin, bool(args.get("keep_binaries", False)), half,
+                                 int(args.get("frames_in_flight", 1)))
         with sequence_metrics_path.open("wb") as f:
             output = {
                 "source": filepath.stem,
@@ -337,6 +415,9 @@ def create_parser() -> argparse.ArgumentParser:
     parent.add_argument("-c", "--entropy-coder", choices=compressai.available_entropy_coders(),
                         default=compressai.available_entropy_coders()[0], help="entropy coder (default: %(default)s)")
     parent.add_argument("--keep_binaries", action="store_true", help="keep bitstream files in output directory")
+    parent.add_argument("--frames-in-flight", type=int, default=1, metavar="N",
+                        help="code up to N frames' strings on host threads behind the device (same bytes; N frames "
+                             "of delay and staging memory)")
     parent.add_argument("-v", "--verbose", action="store_true", help="verbose mode")
     parent.add_argument("-m", "--metric", type=str, choices=["mse", "ms-ssim"], default="mse",
                         help="metric trained against (default: %(default)s)")

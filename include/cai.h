@@ -894,6 +894,35 @@ int cai_ckbd_indexes(const float* scales, int32_t s_ld, const float* scale_table
 int cai_ckbd_dequantize(const int32_t* symbols, const float* means, int32_t m_ld, int32_t B, int32_t H, int32_t W,
                         int32_t C, int32_t parity, float* y_hat, int32_t yh_ld, void* stream);
 
+/* =======================================================================
+ * The coding front end and back end (csrc/code_front.hip): a pixel-major fp32 latent [B][H W] pixels of C channels,
+ * channel stride ld >= C, to and from the host coder's arrays.  The coder's order is NCHW: symbols / indexes are
+ * dense int32 [B][C][H W], what symbols.reshape(B, -1) yields for a [B, C, H, W] tensor.  One launch each; tiles of
+ * 64 pixels x 64 channels go through LDS so that the float accesses (along the channels) and the integer accesses
+ * (along the pixels) both coalesce; 16 bytes per lane on the float side when C, every ld and the float pointers allow
+ * it, on the integer side when H W % 4 == 0 and the integer pointers are 16-byte aligned, scalar otherwise.
+ * Asynchronous on `stream`, no allocation, no atomics.  CAI_EINVAL before any launch for null pointers, B, H, W or
+ * C below 1, a ld below C, B H W C at or above 2^31.
+ * ======================================================================= */
+/* symbols = (int)rint(x - means) and indexes in the coder's order, x_hat = symbols + means pixel-major.
+ *   scales non-NULL (GaussianConditional): means per element with stride m_ld (scales and means may be the channel
+ *     halves of one buffer, ld = 2 C); indexes = build_indexes(scales) by the device function of the fused
+ *     autoregressive coder and the checkerboard passes.
+ *   scales NULL (EntropyBottleneck): means is the [C] medians, indexes = the channel; s_ld, m_ld, scale_table,
+ *     n_scales and scale_bound are not read.
+ *   x NULL (scales non-NULL): indexes only; means, x_hat and symbols are not touched and may be NULL. */
+int cai_code_front(const float* x, int32_t x_ld, const float* scales, int32_t s_ld, const float* means,
+                   int32_t m_ld, const float* scale_table, int32_t n_scales, float scale_bound, int32_t B, int32_t H,
+                   int32_t W, int32_t C, float* x_hat, int32_t xh_ld, int32_t* symbols, int32_t* indexes,
+                   void* stream);
+/* Decoder, before the coder: build_indexes(scales) in the coder's order (cai_code_front with a null x). */
+int cai_code_indexes(const float* scales, int32_t s_ld, const float* scale_table, int32_t n_scales, float scale_bound,
+                     int32_t B, int32_t H, int32_t W, int32_t C, int32_t* indexes, void* stream);
+/* Decoder, after the coder: x_hat = float(symbols) + means pixel-major, the symbols read in the coder's order.
+ * m_ld >= C: means per element; m_ld == 0: means is the [C] per-channel vector. */
+int cai_code_back(const int32_t* symbols, const float* means, int32_t m_ld, int32_t B, int32_t H, int32_t W,
+                  int32_t C, float* x_hat, int32_t xh_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
