@@ -1063,6 +1063,7 @@ extern "C" {
 
 int cai_gdn_reparam(const float* beta_raw, const float* gamma_raw, int32_t C, float beta_min, float reparam_offset,
                     int dtype, float* beta, void* gamma_op, void* stream) {
+    CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "gdn_reparam: bad dtype %d", dtype);
     CAI_CHECK_ARG(beta_raw && gamma_raw && beta && gamma_op && C > 0, "gdn_reparam: bad arguments");
     const float ped = reparam_offset * reparam_offset;
     const float bbound = sqrtf(beta_min + ped), gbound = sqrtf(0.f + ped);
@@ -1119,6 +1120,11 @@ int cai_gdn_param_grad(int dtype, const void* x, int32_t x_ld, const void* u, in
                        const float* beta_raw, const float* gamma_raw, float beta_min, float reparam_offset,
                        float* dbeta_raw, float* dgamma_raw, int32_t accumulate, void* workspace, size_t ws_bytes,
                        void* stream) {
+    CAI_CHECK_ARG(dtype == CAI_BF16 || dtype == CAI_F32, "gdn_param_grad: bad dtype %d", dtype);
+    CAI_CHECK_ARG(gdn_c_ok(C, dtype), "gdn_param_grad: unsupported channel count %d", C);
+    CAI_CHECK_ARG(x && u && beta_raw && gamma_raw && dbeta_raw && dgamma_raw && workspace,
+                  "gdn_param_grad: null pointer");
+    CAI_CHECK_ARG(x_ld >= C && x_ld % 8 == 0, "gdn_param_grad: bad leading dimension %d", x_ld);
     CAI_CHECK_ARG(npix > 0 && npix < (1ll << 31), "gdn_param_grad: bad pixel count");
     CAI_CHECK_ARG(ws_bytes >= cai_gdn_param_grad_workspace_bytes(npix, C, dtype), "gdn_param_grad: workspace too small");
     const cai_conv_geom g = gdn_geom(npix, C);

@@ -85,6 +85,44 @@ def test_gdn_channel_counts_validated(native):
         native.lib.cai_gdn_fwd(native.BF16, None, 48, 16, 48, None, None, 0, None, 48, None)
 
 
+def test_gdn_reparam_and_param_grad_arguments_validated(native):
+    """cai_gdn_reparam refuses a dtype that is neither bf16 nor fp32 (its kernel would store fp32 through a buffer
+    sized for whatever the caller meant); cai_gdn_param_grad refuses null pointers, a channel count outside
+    GDN_DISPATCH and a row pitch below C or off the 16-byte grid.  All before any launch: the pointers are not
+    device memory."""
+    lib = native.lib.load()
+    NN, F, BF, big = ctypes.c_void_p(4096), native.F32, native.BF16, 1 << 30
+    bad = [
+        ("reparam dtype", lambda: lib.cai_gdn_reparam(NN, NN, 32, 1e-6, 2.0 ** -18, 7, NN, NN, None), b"dtype"),
+        ("reparam null", lambda: lib.cai_gdn_reparam(NN, None, 32, 1e-6, 2.0 ** -18, BF, NN, NN, None), b"bad arguments"),
+        ("param_grad dtype", lambda: lib.cai_gdn_param_grad(7, NN, 32, NN, 64, 32, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0, NN,
+                                                            big, None), b"dtype"),
+        ("param_grad C", lambda: lib.cai_gdn_param_grad(BF, NN, 48, NN, 64, 48, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0, NN,
+                                                        big, None), b"channel count"),
+        ("param_grad C fp32", lambda: lib.cai_gdn_param_grad(F, NN, 224, NN, 64, 224, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0,
+                                                             NN, big, None), b"channel count"),
+        ("param_grad x_ld", lambda: lib.cai_gdn_param_grad(BF, NN, 24, NN, 64, 32, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0, NN,
+                                                           big, None), b"leading dimension"),
+        ("param_grad x_ld % 8", lambda: lib.cai_gdn_param_grad(BF, NN, 36, NN, 64, 32, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0,
+                                                               NN, big, None), b"leading dimension"),
+        ("param_grad npix", lambda: lib.cai_gdn_param_grad(BF, NN, 32, NN, 0, 32, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0, NN,
+                                                           big, None), b"pixel count"),
+        ("param_grad workspace", lambda: lib.cai_gdn_param_grad(BF, NN, 32, NN, 64, 32, NN, NN, 1e-6, 2.0 ** -18, NN, NN, 0,
+                                                                NN, 16, None), b"workspace"),
+    ]
+    for i in range(7):                       # x, u, beta_raw, gamma_raw, dbeta_raw, dgamma_raw, workspace
+        p = [NN] * 7
+        p[i] = None
+        bad.append((f"param_grad null {i}",
+                    lambda p=p: lib.cai_gdn_param_grad(BF, p[0], 32, p[1], 64, 32, p[2], p[3], 1e-6, 2.0 ** -18, p[4],
+                                                       p[5], 0, p[6], big, None), b"null"))
+    for name, call, fragment in bad:
+        rc = call()
+        msg = lib.cai_last_error()
+        assert rc == native.CAI_EINVAL, (name, rc, msg)
+        assert msg and fragment in msg, (name, msg)
+
+
 def test_product_path_has_no_cpu_fallback():
     """A CPU tensor must be refused, not silently computed by torch."""
     import torch
